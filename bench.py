@@ -27,6 +27,8 @@ Extra objects on that line:
                 march (TrainHarness.tune_comm, untimed, before the warm-up) with the choices made, and the step time the
                 opt-in bf16 wire format would give (reported only)
 Defaults: N = 1, 20 warm-up + 200 timed steps (0.13 s), then the render / graph / CPU legs: about a minute in all.
+--dump-outputs DIR writes what the last timed step computed as DIR/<name>.npy (dump_outputs below): the inputs are
+seeded, so two builds run with the same arguments can be compared output for output.
 """
 import argparse
 import json
@@ -143,6 +145,8 @@ def parse():
     ap.add_argument("--force-device", type=int, default=None, help="put every rank on this device index")
     ap.add_argument("--mlp-exact", action="store_true",
                     help="development: the main region on the exact-fp32 MFMA kernels (enerf_mlp32_precision(0))")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed as DIR/<name>.npy (rank 0)")
     return ap.parse_args()
 
 
@@ -157,6 +161,22 @@ def build_batches(n_batches, n_rays, device, rank, bound):
         target = (0.5 + 0.5 * torch.sin(rd * 4.0 + ro)).clamp(0, 1).contiguous()
         batches.append((ro, rd, target))
     return batches
+
+
+def dump_outputs(dirname, inputs, loss, samples):
+    """--dump-outputs: the last timed step as its caller sees it, so that two builds can be compared output for output --
+    the step's inputs (`inputs`: name -> tensor), the loss the step returned, and the ray samples the timed region
+    marched in all.  float32 (float64 for the count).  The model's parameters are left out on purpose: the table
+    gradient and the loss are summed in an order that changes from run to run (atomics, as in the reference's kernels),
+    and Adam at eps = 1e-15 turns that last-bit noise on near-zero gradients into whole learning-rate steps, so the
+    parameters after K steps differ between two runs of the same build by far more than rounding."""
+    import numpy as np
+    os.makedirs(dirname, exist_ok=True)
+    arrays = {"input." + k: v for k, v in inputs.items()}
+    arrays["loss"] = loss.detach().reshape(1)
+    for name, t in arrays.items():
+        np.save(os.path.join(dirname, name + ".npy"), t.detach().float().cpu().numpy())
+    np.save(os.path.join(dirname, "timed_samples.npy"), np.array([samples], np.float64))
 
 
 def pmc_traffic(points_per_launch):
@@ -520,7 +540,7 @@ def main():
                 runs[-1][3] = ev
             runs.append([cls, 0, ev, None])
         runs[-1][1] += 1
-        one_step(i)
+        last_loss = one_step(i)
         if per_step is not None:      # the per-step bookkeeping the running total replaces (one tiny launch per render)
             slot = getattr(model, "rendered_counter_slot", None)
             slot = (model.local_step - 1) % 16 if slot is None else slot
@@ -557,6 +577,13 @@ def main():
         dist.all_reduce(samples_acc, op=dist.ReduceOp.SUM)
     elapsed = float(elapsed.item())
     total_samples = int(samples_acc.item())
+    if args.dump_outputs and rank == 0:      # (before the legs below train the same model further)
+        last = args.warmup + args.steps - 1
+        if args.mode == "rgb":
+            inputs = dict(zip(("rays_o", "rays_d", "target"), batches[last % len(batches)]))
+        else:                                       # (cached by the step itself: no new draw)
+            inputs = {k: v for k, v in event_data(last).items() if k != "images"}
+        dump_outputs(args.dump_outputs, inputs, last_loss, total_samples)
     renders_per_step = 2 if args.mode == "events" else 1
     total_rays = world * args.rays * renders_per_step * args.steps
 

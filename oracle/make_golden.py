@@ -15,10 +15,14 @@ import argparse
 import os
 import sys
 
-import numpy as np
-import torch
+# the CPU settings tests/conftest.py pins for the suite: fixtures hold the same bits on every x86 machine
+os.environ["MKL_CBWR"] = "COMPATIBLE,STRICT"
+os.environ["OMP_NUM_THREADS"] = "8"
 
-from . import ref_import
+import numpy as np  # noqa: E402
+import torch  # noqa: E402
+
+from . import ref_import  # noqa: E402
 
 OUT = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests", "golden")
 

@@ -1,7 +1,16 @@
 import os
 import sys
 
-import pytest
+# The host tests hold torch's CPU results to fixtures bit for bit or within a few ulp, and the data-parallel tests hold
+# worker processes to the parent's bits.  Left alone, MKL (torch's CPU BLAS and its vectorised log / exp) picks its code
+# path by CPU model, and CPU GEMMs split their sums by the thread count, which follows the core count: the last bits
+# move with the machine.  MKL's conditional-numerical-reproducibility branch and a fixed intra-op thread count (spawned
+# workers inherit both) give the same bits on every x86 machine.  oracle/make_golden.py mints the fixtures under the
+# same settings.  (Both are read when torch loads: before any test module imports it.)
+os.environ["MKL_CBWR"] = "COMPATIBLE,STRICT"
+os.environ["OMP_NUM_THREADS"] = "8"
+
+import pytest  # noqa: E402
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 if ROOT not in sys.path:
