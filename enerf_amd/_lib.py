@@ -128,6 +128,13 @@ SIGNATURES = {
     "enerf_debug_fold_reduce": [_int],
     "enerf_nerf_mlp_forward": [_vp, _vp, _vp, _vp, _u32, _u32, _u32, _vp, _vp, _u32, _vp],
     "enerf_nerf_mlp_backward": [_vp, _vp, _f32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _u32, _u32, _u32, _u32, _vp, _u32, _vp],
+    "enerf_stratified_points": [_vp, _vp, _vp, _u32, _u32, _f32, _f32, _f32, _vp, _vp, _vp, _vp, _vp, _vp],
+    "enerf_stratified_weights": [_vp, _vp, _vp, _vp, _u32, _u32, _f32, _f32, _vp, _vp, _vp, _vp, _vp],
+    "enerf_stratified_color_input": [_vp, _vp, _vp, _vp, _vp, _u32, _u32, _u32, _vp, _vp],
+    "enerf_stratified_composite_forward": [_vp, _vp, _vp, _vp, _vp, _vp, _u32, _u32, _u32, _u32, _vp, _vp],
+    "enerf_stratified_composite_backward": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _u32, _u32, _u32, _u32,
+                                            _f32, _f32, _u32, _vp, _vp, _vp],
+    "enerf_stratified_scatter_geo_grad": [_vp, _vp, _vp, _vp, _u32, _u32, _vp, _vp],
 }
 
 F32, F16, BF16 = 0, 1, 2

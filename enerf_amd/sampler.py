@@ -9,11 +9,12 @@ reference-minted fixtures (tests/golden/ref_run_*.npz) and against the native co
     resample_depths      inverse-CDF draw of extra depths where the coarse weights are large
     render_stratified    the whole render: depths -> density -> [resample -> density -> merge] -> colour -> pixel
 
-Nothing here is on the MI355X hot path (that is run_cuda: renderer.py / fused_render.py / frame.py).
+On the MI355X (CUDA fp32 rays, nerf/network.py nets, upsample_steps = 0, no background model, autocast off)
+render_stratified hands the whole render to stratified.py: the same statement as one native autograd node.
 """
 import torch
 
-from . import raymarching
+from . import raymarching, stratified
 
 
 def stratified_depths(nears, fars, n, jitter):
@@ -68,6 +69,8 @@ def _points(rays_o, rays_d, z, aabb):
 
 def render_stratified(model, rays_o, rays_d, num_steps=128, upsample_steps=128, bg_color=None, perturb=False, **kwargs):
     """-> {"depth": [...], "image": [..., out_dim_color]} for rays of any leading shape."""
+    if stratified.supported(model, rays_o, rays_d, upsample_steps, bg_color, kwargs.get("out_dim_color")):
+        return stratified.render(model, rays_o, rays_d, num_steps, bg_color, perturb)
     lead = rays_o.shape[:-1]
     rays_o = rays_o.contiguous().view(-1, 3)
     rays_d = rays_d.contiguous().view(-1, 3)

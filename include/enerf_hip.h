@@ -51,8 +51,9 @@ const char* enerf_last_error(void);
 /* ABI version of this header; bumped on any signature change.  This #define is the ONE place the number lives:
  * the library returns it (csrc/runtime.hip), enerf_amd/_lib.py parses it and refuses a library that answers differently,
  * __graft_entry__.build() and tests/test_abi.py compare against the parsed value.
- * 2: enerf_train_step_args lost its RCCL-tail fields, enerf_dp_* retired, enerf_nerf_mlp_* added. */
-#define ENERF_ABI_VERSION 2
+ * 2: enerf_train_step_args lost its RCCL-tail fields, enerf_dp_* retired, enerf_nerf_mlp_* added.
+ * 3: enerf_stratified_* added (the stratified sampler of NeRFRenderer.run). */
+#define ENERF_ABI_VERSION 3
 int enerf_abi_version(void);
 /* The library keeps grow-only scratch buffers per device (march chunk log, grid-backward record lists, ...).  Growing one
  * frees the old allocation; the counter returned here moves every time that happens.  A caller that captured library
@@ -807,6 +808,48 @@ int enerf_prof_sample_every(uint32_t n);
 int enerf_prof_read_units(int kernel_id, double* units, uint64_t* calls_seen);
 /* Synchronises the recorded events; returns total milliseconds and launch count for `kernel_id`. [host ptrs] */
 int enerf_prof_read(int kernel_id, double* total_ms, uint64_t* launches);
+
+/* ------------------------------------------------------------------ stratified sampler (cuda_ray off)
+ * NeRFRenderer.run with upsample_steps = 0 (nerf/renderer.py:150-278; enerf_amd/sampler.py), csrc/stratified.hip.  One
+ * wavefront per ray; N rays of T samples, sample s = n * T + k; all float tensors fp32, contiguous.
+ *
+ * points: near / far of every ray (enerf_near_far_from_aabb's arithmetic) into nears / fars [N], the depths z [N,T]
+ * (torch.linspace(0, 1, T) on the device, with step lin_step = 1 / (T - 1) rounded to fp32, near + (far - near) * g, plus
+ * (u - 0.5) * width when u [N,T] is given; width = (far - near) * inv_T) and the points clamped to the box, xyz [N*T,3]:
+ * bit-equal with sampler.stratified_depths + sampler._points. */
+int enerf_stratified_points(const float* rays_o, const float* rays_d, const float* aabb, uint32_t N, uint32_t T,
+                            float min_near, float lin_step, float inv_T, const float* u, float* nears, float* fars,
+                            float* z, float* xyz, enerf_stream_t stream);
+/* weights: alpha = 1 - exp(-step * density_scale * sigma) (step: next depth minus this one, the last one width),
+ * w = alpha * exclusive product of (1 - alpha + 1e-15) [N,T], opacity = sum w [N], depth = sum w * clamp((z - near) /
+ * (far - near), 0, 1) [N], count [N] = samples with w > 1e-4 per ray.  The compact list of masked samples is ordered by
+ * ray, then depth; its offsets are the inclusive scan `incl` of count (int32, on the device: incl[N-1] is its length). */
+int enerf_stratified_weights(const float* z, const float* sigma, const float* nears, const float* fars, uint32_t N,
+                             uint32_t T, float inv_T, float density_scale, float* w, float* opacity, float* depth,
+                             int32_t* count, enerf_stream_t stream);
+/* The colour net's input rows of the compact list, cin [cap,32] (cap >= N*T): [0 | h16[s,1..15] | SH4(rays_d[n])] -- the
+ * row order enerf_mlp32_*_p read with w0_cols 31, nerf_perm 1.  h16 [N*T,16]: the sigma net's outputs.  Rows incl[N-1]
+ * up to the next multiple of 32 are zeroed (the MLP kernels' valid-row count covers whole 32-row tiles). */
+int enerf_stratified_color_input(const float* w, const int32_t* incl, const int32_t* count, const float* h16,
+                                 const float* rays_d, uint32_t N, uint32_t T, uint32_t cap, float* cin,
+                                 enerf_stream_t stream);
+/* image [N,C] = sum over masked samples of w * rgb + (1 - opacity) * bg; rgb [cap,C] by compact row; bg [C]
+ * (bg_per_ray 0) or [N,C] (bg_per_ray 1); C = 1..3. */
+int enerf_stratified_composite_forward(const float* w, const int32_t* incl, const int32_t* count, const float* opacity,
+                                       const float* rgb, const float* bg, uint32_t bg_per_ray, uint32_t N, uint32_t T,
+                                       uint32_t C, float* image, enerf_stream_t stream);
+/* From g_image [N,C] and g_depth [N] (NULL: depth takes no part in the loss): g_sigma [N*T] for every sample and g_rgb
+ * [cap,C] for the compact rows (the rows up to the next multiple of 32 zeroed).  No division by 1 - alpha + 1e-15. */
+int enerf_stratified_composite_backward(const float* g_image, const float* g_depth, const float* z, const float* sigma,
+                                        const float* w, const float* nears, const float* fars, const int32_t* incl,
+                                        const int32_t* count, const float* rgb, const float* bg, uint32_t bg_per_ray,
+                                        uint32_t N, uint32_t T, uint32_t C, float inv_T, float density_scale,
+                                        uint32_t cap, float* g_sigma, float* g_rgb, enerf_stream_t stream);
+/* dh16 [N*T,16]: columns 0..15 of the colour net's input gradient dx [cap,32] (nerf_perm layout: 1..15 are geo_feat) at
+ * the masked samples' rows, zero elsewhere -- the sigma net's output gradient (its backward replaces column 0 by
+ * dsigma * exp(clamp(h0, -15, 15))). */
+int enerf_stratified_scatter_geo_grad(const float* w, const int32_t* incl, const int32_t* count, const float* dx,
+                                      uint32_t N, uint32_t T, float* dh16, enerf_stream_t stream);
 
 #ifdef __cplusplus
 }
