@@ -59,6 +59,7 @@ SIGNATURES = {
     "enerf_debug_workspace_ordering": [_int],
     "enerf_mlp32_valid_rows": [_vp],
     "enerf_mlp32_valid_rows_ex": [_vp, _u32, _u32],
+    "enerf_mlp32_io16": [_int],
     "enerf_grid_adam_from_records_ex": [_vp, _vp, _vp, _vp, _vp, _u32, _u32, _f32, _f32, _f32, _f32, _u32, _u32, _vp, _vp,
                                         _vp, _vp, _vp, _vp, _vp, _vp],
     "enerf_grid_adam_from_records": [_vp, _vp, _vp, _vp, _vp, _u32, _u32, _f32, _f32, _f32, _f32, _u32, _vp],
@@ -135,6 +136,11 @@ SIGNATURES = {
     "enerf_stratified_composite_backward": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _u32, _u32, _u32, _u32,
                                             _f32, _f32, _u32, _vp, _vp, _vp],
     "enerf_stratified_scatter_geo_grad": [_vp, _vp, _vp, _vp, _u32, _u32, _vp, _vp],
+    "enerf_stratified_color_input_ex": [_vp, _vp, _vp, _vp, _vp, _u32, _u32, _u32, _vp, _u32, _vp],
+    "enerf_stratified_composite_forward_ex": [_vp, _vp, _vp, _vp, _vp, _vp, _u32, _u32, _u32, _u32, _vp, _u32, _vp],
+    "enerf_stratified_composite_backward_ex": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _u32, _u32, _u32,
+                                               _u32, _f32, _f32, _u32, _vp, _vp, _u32, _vp],
+    "enerf_stratified_scatter_geo_grad_ex": [_vp, _vp, _vp, _vp, _u32, _u32, _vp, _u32, _vp],
 }
 
 F32, F16, BF16 = 0, 1, 2

@@ -30,6 +30,7 @@ EXTRA = {"ffmlp.hip": _VGPR_FORM, "mlp32s.hip": _VGPR_FORM, "mlp32s_f16.hip": _V
 # development aid: extra -D flags for every file (e.g. ENERF_DEFINES="-DENERF_BIN_TIMING" python -m enerf_amd.build --force)
 FLAGS += os.environ.get("ENERF_DEFINES", "").split()
 HEADERS = [os.path.join(CSRC, "common.h"), os.path.join(CSRC, "ffmlp_common.h"), os.path.join(CSRC, "mlp32_common.h"), os.path.join(CSRC, "mlp32s_ops.h"), os.path.join(CSRC, "mfma_guard.h"),
+           os.path.join(CSRC, "sh_basis.h"), os.path.join(CSRC, "march_lattice.h"), os.path.join(CSRC, "sweep_points.h"),
            os.path.join(_HERE, "..", "include", "enerf_hip.h")]
 
 

@@ -867,6 +867,7 @@ int g_precision = 1;                // enerf_mlp32_precision: 0 = fp32 MFMA (bit
                                     // 3 = fp16 operands (the same kernels on IEEE half: the reference's fp16 regime)
 inline bool ops16() { return g_precision == 2 || g_precision == 3; }
 bool g_io16 = false;                // ffmlp16_forward / _backward: X, Y, dY, dX are 16-bit row-major tensors
+bool g_io16_p = false;              // enerf_mlp32_io16: the same for the enerf_mlp32_*_p calls (fp16 operands only)
 bool g_recompute = true;            // enerf_mlp32_recompute: the split backward recomputes the hidden activations
 // three hidden layers (the FFMLP colour net on 16-bit operands) recompute whatever the switch says: mlp32s.hip has no
 // activation-loading instance of that shape
@@ -904,6 +905,12 @@ int enerf_mlp32_valid_rows_ex(const int32_t* device_count, uint32_t base, uint32
     g_valid_base = device_count ? base : 0;
     g_valid_cap = device_count ? cap : 0;
     return 0;
+}
+
+int enerf_mlp32_io16(int on) {
+    const int prev = g_io16_p ? 1 : 0;
+    if (on >= 0) g_io16_p = on != 0;
+    return prev;
 }
 
 // Arithmetic of the mlp32 kernels: 0 = v_mfma_f32_32x32x2_f32 (every dot product an fp32 fmaf chain, bit-comparable
@@ -1082,8 +1089,18 @@ int enerf_mlp32_forward_p(const float* X, const float* const* wseg, uint32_t w0_
     w.valid_rows = g_valid_rows;
     w.valid_base = g_valid_base;
     w.valid_cap = g_valid_cap;
-    return mlp32_forward_impl(X, w, B, in_dim, out_dim, num_hidden, activation, output_activation, fb, Y, x_layout,
-                              y_stride, y0_exp, sh_dirs, stream);
+    if (!g_io16_p)
+        return mlp32_forward_impl(X, w, B, in_dim, out_dim, num_hidden, activation, output_activation, fb, Y, x_layout,
+                                  y_stride, y0_exp, sh_dirs, stream);
+    if (g_precision != 3) ENERF_BADARG("mlp32_forward_p: 16-bit I/O (enerf_mlp32_io16) serves precision 3 only");
+    if (num_hidden < 2 || out_dim > 16 || x_layout != 0 || sh_dirs || y0_exp || !Y)
+        ENERF_BADARG("mlp32_forward_p: 16-bit I/O needs two or three hidden layers, out_dim <= 16, row-major X, an output "
+                     "Y and no SH / density epilogue");
+    g_io16 = true;
+    const int rc = mlp32_forward_impl(X, w, B, in_dim, out_dim, num_hidden, activation, output_activation, fb, Y, x_layout,
+                                      y_stride, y0_exp, sh_dirs, stream);
+    g_io16 = false;
+    return rc;
 }
 
 // dY [B,out_dim], fb from the forward; bb [num_hidden,Bp,64] scratch (written); dX NULL, [B,32] (x_layout 0) or
@@ -1422,8 +1439,18 @@ int enerf_mlp32_backward_p(const float* dY, const float* X, const float* const* 
     w.valid_base = g_valid_base;
     w.valid_cap = g_valid_cap;
     d.overwrite = overwrite;
-    return mlp32_backward_impl(dY, X, w, fb, B, in_dim, out_dim, num_hidden, activation, bb, dX, d, x_layout, dy_stride,
-                               y_sigmoid, y_sigmoid_stride, dsigma, h0, h0_stride, stream);
+    if (!g_io16_p)
+        return mlp32_backward_impl(dY, X, w, fb, B, in_dim, out_dim, num_hidden, activation, bb, dX, d, x_layout, dy_stride,
+                                   y_sigmoid, y_sigmoid_stride, dsigma, h0, h0_stride, stream);
+    if (g_precision != 3) ENERF_BADARG("mlp32_backward_p: 16-bit I/O (enerf_mlp32_io16) serves precision 3 only");
+    if (num_hidden < 2 || out_dim > 16 || x_layout != 0 || !g_fused_bwd)
+        ENERF_BADARG("mlp32_backward_p: 16-bit I/O needs two or three hidden layers, out_dim <= 16, row-major X and the "
+                     "fused backward");
+    g_io16 = true;
+    const int rc = mlp32_backward_impl(dY, X, w, fb, B, in_dim, out_dim, num_hidden, activation, bb, dX, d, x_layout,
+                                       dy_stride, y_sigmoid, y_sigmoid_stride, dsigma, h0, h0_stride, stream);
+    g_io16 = false;
+    return rc;
 }
 
 }  // extern "C"

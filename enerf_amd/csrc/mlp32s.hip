@@ -258,7 +258,18 @@ __global__ void __launch_bounds__(256, fwd_weights_in_lds(SIG, P) ? 3 : 1) k_mlp
         for (int ib = 0; ib < 2; ib++)
 #pragma unroll
             for (int t = 0; t < 2; t++) o = mmap(WO(ib, t), af[ib][t], o);
-        if (IO16) {
+        if (IO16 && !(out_act == 6 && (y_stride & 3u) == 0)) {
+            // enerf_mlp32_io16 (the colour net of the stratified sampler's fp16 regime): any stride, any output activation,
+            // one 16-bit store per value; the net's output is rounded first, then the activation of it (P == 1 below)
+            if (valid) {
+#pragma unroll
+                for (int q = 0; q < 16; q++) {
+                    const uint32_t r = (uint32_t)nrow(q, h);
+                    if (r < out_dim)
+                        reinterpret_cast<elem16*>(Y)[s * y_stride + r] = (elem16)out_act_fwd(bf16r(o[q]), out_act);
+                }
+            }
+        } else if (IO16) {
             // rows of out_dim <= 16 values: registers 0..3 -> columns 4h .. 4h+3, registers 4..7 -> columns 8 + 4h ..
             if (valid) {
 #pragma unroll
@@ -374,7 +385,10 @@ __global__ void __launch_bounds__(256) k_mlp32s_bwd(DySource dys, const float* _
             const uint32_t o = (uint32_t)(8 * h + e), oc = o < out_dim ? o : out_dim - 1;
             if constexpr (IO16) dy_raw[e] = (float)reinterpret_cast<const elem16*>(dys.dY)[sc * dys.stride + oc];
             else dy_raw[e] = dys.dY[sc * dys.stride + oc];
-            ys_raw[e] = dys.y_sig ? dys.y_sig[sc * dys.y_sig_stride + oc] : 0.0f;
+            if constexpr (IO16)          // (enerf_mlp32_io16: the forward's 16-bit sigmoid output)
+                ys_raw[e] = dys.y_sig ? (float)reinterpret_cast<const elem16*>(dys.y_sig)[sc * dys.y_sig_stride + oc] : 0.0f;
+            else
+                ys_raw[e] = dys.y_sig ? dys.y_sig[sc * dys.y_sig_stride + oc] : 0.0f;
         }
         if (dys.dsigma) {
             ds_raw = dys.dsigma[sc];

@@ -15,12 +15,19 @@
 //                       the compact rows
 //   k_strat_scatter_geo the colour net's input gradient (geo_feat columns) back to the sigma net's output rows
 //
+// Colour rows, rgb, d rgb and the colour net's input gradient exist in two storages (template parameter E): fp32, and
+// fp16 for the fp16 regime (enerf_mlp32_precision 3 with the mlp32 16-bit I/O: DESIGN.md section 4.9).  In fp16 the
+// directions are rounded to half before the SH basis (the reference's SHEncoder casts its inputs to half under autocast)
+// and the basis is evaluated in fp32 on those half inputs and stored as half -- shencoder.hip's __half path, value for
+// value.  Weights, opacity, depth and the compositing stay fp32 in both.
+//
 // One wavefront per ray in every kernel.  The scans cover 64 lanes x 8 consecutive samples = 512 samples per pass; longer
 // rays take several passes with the running product / sum carried from pass to pass.
 //
 // Compiled with -ffp-contract=off, and no fmaf appears below: every product and sum is rounded where torch rounds it
 // (the one fused operation of torch's linspace kernel is evaluated exactly in double and rounded once).
 #include <float.h>
+#include <hip/hip_fp16.h>
 #include <math.h>
 
 #include "common.h"
@@ -41,6 +48,21 @@ __device__ __forceinline__ float tmax(float a, float b) { return (a != a) ? a : 
 __device__ __forceinline__ float tmin(float a, float b) { return (a != a) ? a : (b < a ? b : a); }
 // Tensor.clamp(0, 1), NaN kept
 __device__ __forceinline__ float clamp01(float x) { return (x != x) ? x : (x < 0.0f ? 0.0f : (x > 1.0f ? 1.0f : x)); }
+
+// the two storages of the colour rows / rgb / d rgb / dx: element loads and stores (fp16: round to nearest even)
+__device__ __forceinline__ float ld_e(const float* p) { return *p; }
+__device__ __forceinline__ float ld_e(const __half* p) { return __half2float(*p); }
+__device__ __forceinline__ void st_e(float* p, float v) { *p = v; }
+__device__ __forceinline__ void st_e(__half* p, float v) { *p = __float2half(v); }
+__device__ __forceinline__ uint32_t pack2h(float a, float b) {
+    return (uint32_t)__half_as_ushort(__float2half(a)) | ((uint32_t)__half_as_ushort(__float2half(b)) << 16);
+}
+__device__ __forceinline__ uint4 pack8h(float a0, float a1, float a2, float a3, float a4, float a5, float a6, float a7) {
+    return make_uint4(pack2h(a0, a1), pack2h(a2, a3), pack2h(a4, a5), pack2h(a6, a7));
+}
+__device__ __forceinline__ float lo_h(uint32_t v) { return __half2float(__ushort_as_half((unsigned short)(v & 0xFFFFu))); }
+__device__ __forceinline__ float hi_h(uint32_t v) { return __half2float(__ushort_as_half((unsigned short)(v >> 16))); }
+__device__ __forceinline__ float round_h(float v) { return __half2float(__float2half(v)); }
 
 __device__ __forceinline__ float wave_sum(float v) { return wave_bcast(wave_incl_scan_add(v, 0), kWave - 1); }
 
@@ -182,11 +204,15 @@ __device__ __forceinline__ uint32_t ray_offset(const int32_t* __restrict__ incl,
 // ------------------------------------------------------------------ colour net input of the compact rows
 // Row layout is the one enerf_mlp32_*_p read with nerf_perm = 1 (w0_cols 31): [0 | geo_feat 15 | SH4(d) 16] -- the kernels
 // permute color_net[0].weight ([SH 16 | geo_feat 15] in memory) to match while staging it.  Rows total .. pad32(total) - 1
-// (the last partial tile the MLP kernels process) are zero-filled.
+// (the last partial tile the MLP kernels process) are zero-filled.  E = __half: 64 B rows, the SH basis of the
+// half-rounded direction; geo_feat is the sigma net's fp16-rounded output (precision 3), so its conversion is exact.
+template <typename E>
 __global__ void __launch_bounds__(256) k_strat_color_input(const float* __restrict__ w, const int32_t* __restrict__ incl,
                                                            const int32_t* __restrict__ count, const float* __restrict__ h16,
                                                            const float* __restrict__ rays_d, uint32_t N, uint32_t T,
-                                                           uint32_t cap, ShNorm4 nrm, float* __restrict__ cin) {
+                                                           uint32_t cap, ShNorm4 nrm, E* __restrict__ cin) {
+    constexpr bool kHalf = sizeof(E) == 2;
+    constexpr int kVec = kHalf ? 4 : 8;           // 16-byte pieces per row
     const uint32_t n = blockIdx.x * kRaysPerBlock + (threadIdx.x >> 6);
     const uint32_t lane = threadIdx.x & 63;
     if (n >= N) return;
@@ -195,11 +221,22 @@ __global__ void __launch_bounds__(256) k_strat_color_input(const float* __restri
         const uint32_t end = min((total + 31u) & ~31u, cap);
         for (uint32_t r = total + lane; r < end; r += kWave)
 #pragma unroll
-            for (int q = 0; q < 8; q++) reinterpret_cast<float4*>(cin + (size_t)r * 32)[q] = make_float4(0.f, 0.f, 0.f, 0.f);
+            for (int q = 0; q < kVec; q++) reinterpret_cast<uint4*>(cin + (size_t)r * 32)[q] = make_uint4(0u, 0u, 0u, 0u);
     }
     if (count[n] == 0) return;
     float sh[16];
-    sh4(rays_d[n * 3], rays_d[n * 3 + 1], rays_d[n * 3 + 2], nrm, sh);
+    float d0 = rays_d[n * 3], d1 = rays_d[n * 3 + 1], d2 = rays_d[n * 3 + 2];
+    if (kHalf) {
+        d0 = round_h(d0);
+        d1 = round_h(d1);
+        d2 = round_h(d2);
+    }
+    sh4(d0, d1, d2, nrm, sh);
+    uint4 shh[2];
+    if (kHalf) {
+        shh[0] = pack8h(sh[0], sh[1], sh[2], sh[3], sh[4], sh[5], sh[6], sh[7]);
+        shh[1] = pack8h(sh[8], sh[9], sh[10], sh[11], sh[12], sh[13], sh[14], sh[15]);
+    }
     const float* wr = w + (size_t)n * T;
     uint32_t off = ray_offset(incl, count, n);
     for (uint32_t base = 0; base < T; base += kPass) {
@@ -210,28 +247,37 @@ __global__ void __launch_bounds__(256) k_strat_color_input(const float* __restri
             if (!(bits & (1u << i))) continue;
             const size_t s = (size_t)n * T + k0 + i;
             const float4* src = reinterpret_cast<const float4*>(h16 + s * 16);
-            float4* dst = reinterpret_cast<float4*>(cin + (size_t)row * 32);
             float4 q0 = src[0];
             q0.x = 0.0f;                          // raw density: zero weight in the colour net, kept finite
-            dst[0] = q0;
-            dst[1] = src[1];
-            dst[2] = src[2];
-            dst[3] = src[3];
-            dst[4] = make_float4(sh[0], sh[1], sh[2], sh[3]);
-            dst[5] = make_float4(sh[4], sh[5], sh[6], sh[7]);
-            dst[6] = make_float4(sh[8], sh[9], sh[10], sh[11]);
-            dst[7] = make_float4(sh[12], sh[13], sh[14], sh[15]);
+            if constexpr (kHalf) {
+                const float4 q1 = src[1], q2 = src[2], q3 = src[3];
+                uint4* dst = reinterpret_cast<uint4*>(cin + (size_t)row * 32);
+                dst[0] = pack8h(q0.x, q0.y, q0.z, q0.w, q1.x, q1.y, q1.z, q1.w);
+                dst[1] = pack8h(q2.x, q2.y, q2.z, q2.w, q3.x, q3.y, q3.z, q3.w);
+                dst[2] = shh[0];
+                dst[3] = shh[1];
+            } else {
+                float4* dst = reinterpret_cast<float4*>(cin + (size_t)row * 32);
+                dst[0] = q0;
+                dst[1] = src[1];
+                dst[2] = src[2];
+                dst[3] = src[3];
+                dst[4] = make_float4(sh[0], sh[1], sh[2], sh[3]);
+                dst[5] = make_float4(sh[4], sh[5], sh[6], sh[7]);
+                dst[6] = make_float4(sh[8], sh[9], sh[10], sh[11]);
+                dst[7] = make_float4(sh[12], sh[13], sh[14], sh[15]);
+            }
             row++;
         }
     }
 }
 
 // ------------------------------------------------------------------ compositing: forward
-// bg: [C] (bg_per_ray 0) or [N, C] (bg_per_ray 1)
-template <int C>
+// bg: [C] (bg_per_ray 0) or [N, C] (bg_per_ray 1); rgb in storage E, accumulated in fp32
+template <int C, typename E>
 __global__ void __launch_bounds__(256) k_strat_composite(const float* __restrict__ w, const int32_t* __restrict__ incl,
                                                          const int32_t* __restrict__ count,
-                                                         const float* __restrict__ opacity, const float* __restrict__ rgb,
+                                                         const float* __restrict__ opacity, const E* __restrict__ rgb,
                                                          const float* __restrict__ bg, uint32_t bg_per_ray, uint32_t N,
                                                          uint32_t T, float* __restrict__ image) {
     const uint32_t n = blockIdx.x * kRaysPerBlock + (threadIdx.x >> 6);
@@ -251,7 +297,7 @@ __global__ void __launch_bounds__(256) k_strat_composite(const float* __restrict
                 if (!(bits & (1u << i))) continue;
                 const float wk = wr[k0 + i];
 #pragma unroll
-                for (int ch = 0; ch < C; ch++) acc[ch] += wk * rgb[(size_t)row * C + ch];
+                for (int ch = 0; ch < C; ch++) acc[ch] += wk * ld_e(rgb + (size_t)row * C + ch);
                 row++;
             }
         }
@@ -274,13 +320,14 @@ __global__ void __launch_bounds__(256) k_strat_composite(const float* __restrict
 // a reverse linear recurrence, evaluated as a scan of affine maps (lane chunks, then across the wave, then pass to pass).
 // Nothing is divided by (1 - alpha + 1e-15).  dL/dsigma_k = dL/dalpha_k * step_k * s * exp(-step_k * s * sigma_k).
 // g_sigma doubles as the store of T_k between the two sweeps when the ray takes more than one pass.
-template <int C>
+// rgb and g_rgb in storage E (fp16: d rgb = g * w rounded to half, the gradient of the reference's `h.to(fp32)`).
+template <int C, typename E>
 __global__ void __launch_bounds__(256) k_strat_composite_bwd(
     const float* __restrict__ g_image, const float* __restrict__ g_depth, const float* __restrict__ z,
     const float* __restrict__ sigma, const float* __restrict__ w, const float* __restrict__ nears,
     const float* __restrict__ fars, const int32_t* __restrict__ incl, const int32_t* __restrict__ count,
-    const float* __restrict__ rgb, const float* __restrict__ bg, uint32_t bg_per_ray, uint32_t N, uint32_t T,
-    float inv_T, float density_scale, uint32_t cap, float* __restrict__ g_sigma, float* __restrict__ g_rgb) {
+    const E* __restrict__ rgb, const float* __restrict__ bg, uint32_t bg_per_ray, uint32_t N, uint32_t T,
+    float inv_T, float density_scale, uint32_t cap, float* __restrict__ g_sigma, E* __restrict__ g_rgb) {
     const uint32_t n = blockIdx.x * kRaysPerBlock + (threadIdx.x >> 6);
     const uint32_t lane = threadIdx.x & 63;
     if (n >= N) return;
@@ -289,7 +336,7 @@ __global__ void __launch_bounds__(256) k_strat_composite_bwd(
         const uint32_t end = min((total + 31u) & ~31u, cap);
         for (uint32_t r = total + lane; r < end; r += kWave)
 #pragma unroll
-            for (int ch = 0; ch < C; ch++) g_rgb[(size_t)r * C + ch] = 0.0f;
+            for (int ch = 0; ch < C; ch++) st_e(g_rgb + (size_t)r * C + ch, 0.0f);
     }
     const float near = nears[n], far = fars[n];
     const float span = far - near, width = span * inv_T;
@@ -362,8 +409,8 @@ __global__ void __launch_bounds__(256) k_strat_composite_bwd(
                     const float wk = wr[k];
 #pragma unroll
                     for (int ch = 0; ch < C; ch++) {
-                        qk += gi[ch] * rgb[(size_t)row * C + ch];
-                        g_rgb[(size_t)row * C + ch] = gi[ch] * wk;
+                        qk += gi[ch] * ld_e(rgb + (size_t)row * C + ch);
+                        st_e(g_rgb + (size_t)row * C + ch, gi[ch] * wk);
                     }
                     row++;
                 }
@@ -408,8 +455,10 @@ __global__ void __launch_bounds__(256) k_strat_composite_bwd(
 // ------------------------------------------------------------------ geo_feat gradient back to the sigma net's rows
 // dh16 [N*T, 16]: columns 1..15 = the colour net's input gradient of the compact row (columns 1..15 of dx, nerf_perm
 // layout), zero off the mask; column 0 is left for the sigma net's backward, which replaces it (dsigma * exp(h0)).
+// dx in storage E (fp16: the colour net's 16-bit dX, widened exactly).
+template <typename E>
 __global__ void __launch_bounds__(256) k_strat_scatter_geo(const float* __restrict__ w, const int32_t* __restrict__ incl,
-                                                           const int32_t* __restrict__ count, const float* __restrict__ dx,
+                                                           const int32_t* __restrict__ count, const E* __restrict__ dx,
                                                            uint32_t N, uint32_t T, float* __restrict__ dh16) {
     const uint32_t n = blockIdx.x * kRaysPerBlock + (threadIdx.x >> 6);
     const uint32_t lane = threadIdx.x & 63;
@@ -424,9 +473,19 @@ __global__ void __launch_bounds__(256) k_strat_scatter_geo(const float* __restri
             if (k0 + i >= T) break;
             float4* dst = reinterpret_cast<float4*>(dh16 + ((size_t)n * T + k0 + i) * 16);
             if (bits & (1u << i)) {
-                const float4* src = reinterpret_cast<const float4*>(dx + (size_t)row * 32);
+                if constexpr (sizeof(E) == 2) {
+                    const uint4* src = reinterpret_cast<const uint4*>(dx + (size_t)row * 32);
 #pragma unroll
-                for (int q = 0; q < 4; q++) dst[q] = src[q];
+                    for (int q = 0; q < 2; q++) {
+                        const uint4 v = src[q];
+                        dst[2 * q] = make_float4(lo_h(v.x), hi_h(v.x), lo_h(v.y), hi_h(v.y));
+                        dst[2 * q + 1] = make_float4(lo_h(v.z), hi_h(v.z), lo_h(v.w), hi_h(v.w));
+                    }
+                } else {
+                    const float4* src = reinterpret_cast<const float4*>(dx + (size_t)row * 32);
+#pragma unroll
+                    for (int q = 0; q < 4; q++) dst[q] = src[q];
+                }
                 row++;
             } else {
 #pragma unroll
@@ -467,31 +526,94 @@ int enerf_stratified_weights(const float* z, const float* sigma, const float* ne
     return 0;
 }
 
+int enerf_stratified_color_input_ex(const float* w, const int32_t* incl, const int32_t* count, const float* h16,
+                                    const float* rays_d, uint32_t N, uint32_t T, uint32_t cap, void* cin, uint32_t storage,
+                                    enerf_stream_t stream) {
+    if (!w || !incl || !count || !h16 || !rays_d || !cin) ENERF_BADARG("stratified_color_input: null pointer");
+    if ((uint64_t)cap < (uint64_t)N * T) ENERF_BADARG("stratified_color_input: cap %u < N * T", cap);
+    if (storage != ENERF_F32 && storage != ENERF_F16) ENERF_BADARG("stratified_color_input: storage must be F32 or F16");
+    if (N == 0) return 0;
+    hipStream_t s = (hipStream_t)stream;
+    if (storage == ENERF_F16)
+        k_strat_color_input<__half><<<ray_blocks(N), 256, 0, s>>>(w, incl, count, h16, rays_d, N, T, cap, make_sh_norm4(),
+                                                                   (__half*)cin);
+    else
+        k_strat_color_input<float><<<ray_blocks(N), 256, 0, s>>>(w, incl, count, h16, rays_d, N, T, cap, make_sh_norm4(),
+                                                                  (float*)cin);
+    ENERF_LAUNCH_CHECK("stratified_color_input");
+    return 0;
+}
+
 int enerf_stratified_color_input(const float* w, const int32_t* incl, const int32_t* count, const float* h16,
                                  const float* rays_d, uint32_t N, uint32_t T, uint32_t cap, float* cin,
                                  enerf_stream_t stream) {
-    if (!w || !incl || !count || !h16 || !rays_d || !cin) ENERF_BADARG("stratified_color_input: null pointer");
-    if ((uint64_t)cap < (uint64_t)N * T) ENERF_BADARG("stratified_color_input: cap %u < N * T", cap);
+    return enerf_stratified_color_input_ex(w, incl, count, h16, rays_d, N, T, cap, cin, ENERF_F32, stream);
+}
+
+int enerf_stratified_composite_forward_ex(const float* w, const int32_t* incl, const int32_t* count,
+                                          const float* opacity, const void* rgb, const float* bg, uint32_t bg_per_ray,
+                                          uint32_t N, uint32_t T, uint32_t C, float* image, uint32_t storage,
+                                          enerf_stream_t stream) {
+    if (!w || !incl || !count || !opacity || !rgb || !bg || !image) ENERF_BADARG("stratified_composite_forward: null pointer");
+    if (storage != ENERF_F32 && storage != ENERF_F16) ENERF_BADARG("stratified_composite_forward: storage must be F32 or F16");
+    if (C < 1 || C > 3) ENERF_BADARG("stratified_composite_forward: C must be 1..3, got %u", C);
     if (N == 0) return 0;
-    k_strat_color_input<<<ray_blocks(N), 256, 0, (hipStream_t)stream>>>(w, incl, count, h16, rays_d, N, T, cap,
-                                                                         make_sh_norm4(), cin);
-    ENERF_LAUNCH_CHECK("stratified_color_input");
+    hipStream_t s = (hipStream_t)stream;
+#define STRAT_FWD(CC, EE) \
+    k_strat_composite<CC, EE><<<ray_blocks(N), 256, 0, s>>>(w, incl, count, opacity, (const EE*)rgb, bg, bg_per_ray, N, T, image)
+#define STRAT_FWD_E(CC)                              \
+    do {                                             \
+        if (storage == ENERF_F16) STRAT_FWD(CC, __half); \
+        else STRAT_FWD(CC, float);                   \
+    } while (0)
+    switch (C) {
+        case 1: STRAT_FWD_E(1); break;
+        case 2: STRAT_FWD_E(2); break;
+        default: STRAT_FWD_E(3); break;
+    }
+#undef STRAT_FWD_E
+#undef STRAT_FWD
+    ENERF_LAUNCH_CHECK("stratified_composite_forward");
     return 0;
 }
 
 int enerf_stratified_composite_forward(const float* w, const int32_t* incl, const int32_t* count, const float* opacity,
                                        const float* rgb, const float* bg, uint32_t bg_per_ray, uint32_t N, uint32_t T,
                                        uint32_t C, float* image, enerf_stream_t stream) {
-    if (!w || !incl || !count || !opacity || !rgb || !bg || !image) ENERF_BADARG("stratified_composite_forward: null pointer");
+    return enerf_stratified_composite_forward_ex(w, incl, count, opacity, rgb, bg, bg_per_ray, N, T, C, image, ENERF_F32,
+                                                 stream);
+}
+
+int enerf_stratified_composite_backward_ex(const float* g_image, const float* g_depth, const float* z, const float* sigma,
+                                           const float* w, const float* nears, const float* fars, const int32_t* incl,
+                                           const int32_t* count, const void* rgb, const float* bg, uint32_t bg_per_ray,
+                                           uint32_t N, uint32_t T, uint32_t C, float inv_T, float density_scale,
+                                           uint32_t cap, float* g_sigma, void* g_rgb, uint32_t storage,
+                                           enerf_stream_t stream) {
+    if (!g_image || !z || !sigma || !w || !nears || !fars || !incl || !count || !rgb || !bg || !g_sigma || !g_rgb)
+        ENERF_BADARG("stratified_composite_backward: null pointer");
+    if ((uint64_t)cap < (uint64_t)N * T) ENERF_BADARG("stratified_composite_backward: cap %u < N * T", cap);
+    if (storage != ENERF_F32 && storage != ENERF_F16) ENERF_BADARG("stratified_composite_backward: storage must be F32 or F16");
+    if (C < 1 || C > 3) ENERF_BADARG("stratified_composite_backward: C must be 1..3, got %u", C);
     if (N == 0) return 0;
     hipStream_t s = (hipStream_t)stream;
+#define STRAT_BWD(CC, EE)                                                                                                 \
+    k_strat_composite_bwd<CC, EE><<<ray_blocks(N), 256, 0, s>>>(g_image, g_depth, z, sigma, w, nears, fars, incl, count,  \
+                                                                (const EE*)rgb, bg, bg_per_ray, N, T, inv_T, density_scale, \
+                                                                cap, g_sigma, (EE*)g_rgb)
+#define STRAT_BWD_E(CC)                              \
+    do {                                             \
+        if (storage == ENERF_F16) STRAT_BWD(CC, __half); \
+        else STRAT_BWD(CC, float);                   \
+    } while (0)
     switch (C) {
-        case 1: k_strat_composite<1><<<ray_blocks(N), 256, 0, s>>>(w, incl, count, opacity, rgb, bg, bg_per_ray, N, T, image); break;
-        case 2: k_strat_composite<2><<<ray_blocks(N), 256, 0, s>>>(w, incl, count, opacity, rgb, bg, bg_per_ray, N, T, image); break;
-        case 3: k_strat_composite<3><<<ray_blocks(N), 256, 0, s>>>(w, incl, count, opacity, rgb, bg, bg_per_ray, N, T, image); break;
-        default: ENERF_BADARG("stratified_composite_forward: C must be 1..3, got %u", C);
+        case 1: STRAT_BWD_E(1); break;
+        case 2: STRAT_BWD_E(2); break;
+        default: STRAT_BWD_E(3); break;
     }
-    ENERF_LAUNCH_CHECK("stratified_composite_forward");
+#undef STRAT_BWD_E
+#undef STRAT_BWD
+    ENERF_LAUNCH_CHECK("stratified_composite_backward");
     return 0;
 }
 
@@ -500,32 +622,28 @@ int enerf_stratified_composite_backward(const float* g_image, const float* g_dep
                                         const int32_t* count, const float* rgb, const float* bg, uint32_t bg_per_ray,
                                         uint32_t N, uint32_t T, uint32_t C, float inv_T, float density_scale,
                                         uint32_t cap, float* g_sigma, float* g_rgb, enerf_stream_t stream) {
-    if (!g_image || !z || !sigma || !w || !nears || !fars || !incl || !count || !rgb || !bg || !g_sigma || !g_rgb)
-        ENERF_BADARG("stratified_composite_backward: null pointer");
-    if ((uint64_t)cap < (uint64_t)N * T) ENERF_BADARG("stratified_composite_backward: cap %u < N * T", cap);
+    return enerf_stratified_composite_backward_ex(g_image, g_depth, z, sigma, w, nears, fars, incl, count, rgb, bg,
+                                                  bg_per_ray, N, T, C, inv_T, density_scale, cap, g_sigma, g_rgb,
+                                                  ENERF_F32, stream);
+}
+
+int enerf_stratified_scatter_geo_grad_ex(const float* w, const int32_t* incl, const int32_t* count, const void* dx,
+                                         uint32_t N, uint32_t T, float* dh16, uint32_t storage, enerf_stream_t stream) {
+    if (!w || !incl || !count || !dx || !dh16) ENERF_BADARG("stratified_scatter_geo_grad: null pointer");
+    if (storage != ENERF_F32 && storage != ENERF_F16) ENERF_BADARG("stratified_scatter_geo_grad: storage must be F32 or F16");
     if (N == 0) return 0;
     hipStream_t s = (hipStream_t)stream;
-#define STRAT_BWD(CC)                                                                                                    \
-    k_strat_composite_bwd<CC><<<ray_blocks(N), 256, 0, s>>>(g_image, g_depth, z, sigma, w, nears, fars, incl, count, rgb, \
-                                                            bg, bg_per_ray, N, T, inv_T, density_scale, cap, g_sigma, g_rgb)
-    switch (C) {
-        case 1: STRAT_BWD(1); break;
-        case 2: STRAT_BWD(2); break;
-        case 3: STRAT_BWD(3); break;
-        default: ENERF_BADARG("stratified_composite_backward: C must be 1..3, got %u", C);
-    }
-#undef STRAT_BWD
-    ENERF_LAUNCH_CHECK("stratified_composite_backward");
+    if (storage == ENERF_F16)
+        k_strat_scatter_geo<__half><<<ray_blocks(N), 256, 0, s>>>(w, incl, count, (const __half*)dx, N, T, dh16);
+    else
+        k_strat_scatter_geo<float><<<ray_blocks(N), 256, 0, s>>>(w, incl, count, (const float*)dx, N, T, dh16);
+    ENERF_LAUNCH_CHECK("stratified_scatter_geo_grad");
     return 0;
 }
 
 int enerf_stratified_scatter_geo_grad(const float* w, const int32_t* incl, const int32_t* count, const float* dx,
                                       uint32_t N, uint32_t T, float* dh16, enerf_stream_t stream) {
-    if (!w || !incl || !count || !dx || !dh16) ENERF_BADARG("stratified_scatter_geo_grad: null pointer");
-    if (N == 0) return 0;
-    k_strat_scatter_geo<<<ray_blocks(N), 256, 0, (hipStream_t)stream>>>(w, incl, count, dx, N, T, dh16);
-    ENERF_LAUNCH_CHECK("stratified_scatter_geo_grad");
-    return 0;
+    return enerf_stratified_scatter_geo_grad_ex(w, incl, count, dx, N, T, dh16, ENERF_F32, stream);
 }
 
 }  // extern "C"

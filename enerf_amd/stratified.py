@@ -14,6 +14,13 @@ the colour MLP's backward on the compact rows, k_strat_scatter_geo (geo_feat gra
 sigma MLP's backward (trunc_exp folded in), the grid backward.  It returns the gradients of the network's own parameters,
 like fused_network._FusedNeRF, so optimisers and the event loop see nothing new.
 
+The fp16 regime: a model whose `mlp_precision` is 3 -- TrainHarness(fp16=True) sets it for its
+steps; for evaluation set `model.mlp_precision = 3` and call `model.render` -- runs both nets on fp16 operands with fp32
+accumulation (enerf_mlp32_precision 3), keeps the colour rows, rgb, d rgb and the colour net's input gradient in fp16
+(enerf_stratified_*_ex with ENERF_F16, enerf_mlp32_io16), rounds the directions to fp16 before the SH basis, and keeps
+points, weights, compositing, the hash table and its gradient in fp32.  Autocast is still refused: under autocast the
+statement runs, as it does in the reference.
+
 What the PyTorch statement does with host synchronisations (`mask.any()`, boolean indexing) happens here on the device, so
 a forward + backward can be captured in a CUDA graph.  Anything this does not serve -- CPU tensors, autocast, FFMLP nets,
 upsampling, the background model, view directions off, out_dim_color > 3 -- keeps the statement (sampler.py).
@@ -31,7 +38,8 @@ from .fused_mlp import pad32
 ENABLED = True
 # renders taken by this route (tests assert that the route was taken)
 stats = {"calls": 0}
-# tests: keep the last render's weights [N,T] and per-ray mask counts [N] in `last` (device tensors, never read here)
+# tests: keep the last render's weights [N,T], per-ray mask counts [N], sigma net outputs [N*T,16], sigma [N*T], colour rows
+# [cap,32] and rgb [cap,C] in `last` (device tensors, never read here; the compact rows beyond incl[-1] are padding)
 KEEP_LAST = False
 last = None
 
@@ -176,32 +184,38 @@ def render_forward(ro, rd, u, bg, per_ray, aabb, geo, train, embeddings, offsets
     total_ptr = incl.data_ptr() + 4 * (N - 1)
 
     # colour on the compact rows only: capacity N*T, the MLP kernels stop at the device count's last 32-row tile
+    # (fp16 regime: the colour rows, rgb and their gradients in half -- 64 B instead of 128 B per masked sample)
+    f16 = prec == 3
+    store, cdt = (L.F16, torch.float16) if f16 else (L.F32, torch.float32)
     cap = B
     capp = pad32(cap)
-    cin = torch.empty(capp, 32, **f32)
-    L.check(lib.enerf_stratified_color_input(w.data_ptr(), incl.data_ptr(), count.data_ptr(), h16.data_ptr(),
-                                             rd.data_ptr(), N, T, cap, cin.data_ptr(), stream), "stratified_color_input")
-    rgb = torch.empty(capp, C, **f32)
-    fb_c = torch.empty(2, capp, 64, **f32) if train else None
+    cin = torch.empty(capp, 32, dtype=cdt, device=dev)
+    L.check(lib.enerf_stratified_color_input_ex(w.data_ptr(), incl.data_ptr(), count.data_ptr(), h16.data_ptr(),
+                                                rd.data_ptr(), N, T, cap, cin.data_ptr(), store, stream),
+            "stratified_color_input")
+    rgb = torch.empty(capp, C, dtype=cdt, device=dev)
+    fb_c = torch.empty(2, capp, 64, **f32) if train and not f16 else None
     lib.enerf_mlp32_valid_rows(total_ptr)
+    lib.enerf_mlp32_io16(1 if f16 else 0)
     try:
         with _fn._precision(prec):
             L.check(lib.enerf_mlp32_forward_p(cin.data_ptr(), seg_c, 31, 1, cap, 32, C, 2, 0, 3,
-                                              fb_c.data_ptr() if train else None, rgb.data_ptr(), 0, 0, None, None,
-                                              stream), "mlp32_forward_p(color)")
-    finally:                                 # the row count is per call: never left behind for another launch
+                                              fb_c.data_ptr() if fb_c is not None else None, rgb.data_ptr(), 0, 0, None,
+                                              None, stream), "mlp32_forward_p(color)")
+    finally:                                 # the row count and the I/O width are per call: never left behind
+        lib.enerf_mlp32_io16(0)
         lib.enerf_mlp32_valid_rows(None)
-    L.check(lib.enerf_stratified_composite_forward(w.data_ptr(), incl.data_ptr(), count.data_ptr(), opacity.data_ptr(),
-                                                   rgb.data_ptr(), bg.data_ptr(), per_ray, N, T, C, image.data_ptr(),
-                                                   stream), "stratified_composite_forward")
+    L.check(lib.enerf_stratified_composite_forward_ex(w.data_ptr(), incl.data_ptr(), count.data_ptr(),
+                                                      opacity.data_ptr(), rgb.data_ptr(), bg.data_ptr(), per_ray, N, T, C,
+                                                      image.data_ptr(), store, stream), "stratified_composite_forward")
     if KEEP_LAST:
-        last = dict(w=w, count=count, incl=incl)
+        last = dict(w=w, count=count, incl=incl, h16=h16, sigma=sigma, cin=cin, rgb=rgb)
     if not train:
         return image, depth, None
     sv = dict(rd=rd, bg=bg, per_ray=per_ray, N=N, T=T, C=C, B=B, cap=cap, inv_T=inv_T, s_dens=s_dens, z=z, xyz=xyz,
               nears=nears, fars=fars, sigma=sigma, h16=h16, feats=feats, fb_s=fb_s, w=w, count=count, incl=incl, cin=cin,
               rgb=rgb, fb_c=fb_c, seg_s=seg_s, seg_c=seg_c, weights=weights, emb=emb, offsets=offsets, param=embeddings,
-              S=S, H=base_resolution, gridtype=gridtype, affine=affine, prec=prec)
+              S=S, H=base_resolution, gridtype=gridtype, affine=affine, prec=prec, store=store, cdt=cdt)
     return image, depth, sv
 
 
@@ -216,30 +230,36 @@ def render_backward(sv, g_image, g_depth):
     g_image = torch.zeros(N, C, **f32) if g_image is None else g_image.float().contiguous().view(N, C)
     g_depth = None if g_depth is None else g_depth.float().contiguous().view(N)
     g_sigma = torch.empty(B, **f32)
-    g_rgb = torch.empty(capp, C, **f32)
+    store, cdt = sv["store"], sv["cdt"]
+    g_rgb = torch.empty(capp, C, dtype=cdt, device=dev)
     incl, count = sv["incl"], sv["count"]
-    L.check(lib.enerf_stratified_composite_backward(
+    L.check(lib.enerf_stratified_composite_backward_ex(
         g_image.data_ptr(), g_depth.data_ptr() if g_depth is not None else None, sv["z"].data_ptr(),
         sv["sigma"].data_ptr(), sv["w"].data_ptr(), sv["nears"].data_ptr(), sv["fars"].data_ptr(), incl.data_ptr(),
         count.data_ptr(), sv["rgb"].data_ptr(), sv["bg"].data_ptr(), sv["per_ray"], N, T, C, sv["inv_T"], sv["s_dens"],
-        cap, g_sigma.data_ptr(), g_rgb.data_ptr(), stream), "stratified_composite_backward")
+        cap, g_sigma.data_ptr(), g_rgb.data_ptr(), store, stream), "stratified_composite_backward")
 
     dw, (dseg_s, dseg_c) = _fn._grad_segments("linear", dev, C)
-    dx = torch.empty(capp, 32, **f32)
-    # (under a valid-row count the colour backward is the fused kernel, which does not touch `bb`)
+    dx = torch.empty(capp, 32, dtype=cdt, device=dev)
+    # (under a valid-row count the colour backward is the fused kernel, which does not touch `bb`; the 16-bit form
+    #  recomputes the hidden activations and reads no `fb`)
     bb_c = torch.empty(1, **f32)
+    fb_c = sv["fb_c"]
     lib.enerf_mlp32_valid_rows(incl.data_ptr() + 4 * (N - 1))
+    lib.enerf_mlp32_io16(1 if store == L.F16 else 0)
     try:
         with _fn._precision(sv["prec"]):
             L.check(lib.enerf_mlp32_backward_p(g_rgb.data_ptr(), sv["cin"].data_ptr(), sv["seg_c"], dseg_c, 31, 1, 1,
-                                               sv["fb_c"].data_ptr(), cap, 32, C, 2, 0, bb_c.data_ptr(), dx.data_ptr(), 0,
-                                               0, sv["rgb"].data_ptr(), C, None, None, 0, stream),
-                    "mlp32_backward_p(color)")
+                                               fb_c.data_ptr() if fb_c is not None else None, cap, 32, C, 2, 0,
+                                               bb_c.data_ptr(), dx.data_ptr(), 0, 0, sv["rgb"].data_ptr(), C, None, None,
+                                               0, stream), "mlp32_backward_p(color)")
     finally:
+        lib.enerf_mlp32_io16(0)
         lib.enerf_mlp32_valid_rows(None)
     dh16 = torch.empty(B, 16, **f32)
-    L.check(lib.enerf_stratified_scatter_geo_grad(sv["w"].data_ptr(), incl.data_ptr(), count.data_ptr(), dx.data_ptr(),
-                                                  N, T, dh16.data_ptr(), stream), "stratified_scatter_geo_grad")
+    L.check(lib.enerf_stratified_scatter_geo_grad_ex(sv["w"].data_ptr(), incl.data_ptr(), count.data_ptr(),
+                                                     dx.data_ptr(), N, T, dh16.data_ptr(), store, stream),
+            "stratified_scatter_geo_grad")
     dfeat = torch.empty(16, Bp, 2, **f32)
     bb_s = torch.empty(1, Bp, 64, **f32)
     with _fn._precision(sv["prec"]):

@@ -82,6 +82,12 @@ class TrainHarness:
         #         what a checkpoint stores and restores.  What is NOT reproduced: the half copy of the hash table
         #         (gridencoder/grid.py:38-39: the gather reads the fp32 table, features are fp32 until the first layer
         #         rounds them).
+        #       * the stratified sampler's fp16 regime (`strat_f16`; one GPU, a `cuda_ray = False` model of network.py
+        #         nets): the same mlp32 precision 3, set for the step by _amp_scope, on the native route of
+        #         stratified.py with its colour rows / rgb in fp16, and the GradScaler's host
+        #         protocol as the reference runs it (scale(loss).backward(), unscale_, step, update) -- no autocast.
+        #         A step that route does not serve (background model, upsample_steps, FFMLP nets, an attached
+        #         averager) takes the autocast route with the same scaler.
         #       * fp16="autocast" (and whatever the closed-form step does not serve): torch.autocast + GradScaler around
         #         the op-by-op route, half hash table + half table gradient (gridencoder/grid.py:38-39,72), half SH.
         #   amp="bf16": NOT the reference's regime, named apart for that reason -- the closed-form step with the networks
@@ -93,7 +99,8 @@ class TrainHarness:
         if amp not in (None, "bf16"):
             raise ValueError(f"amp={amp!r}: None or 'bf16'")
         self.fp16 = bool(fp16)                  # the autocast route (all of it, or the steps the closed form cannot take)
-        self.amp_bf16 = self.amp_f16 = False
+        self.amp_bf16 = self.amp_f16 = self.strat_f16 = False
+        self._f16_autocast = True               # the autocast route's autocast (off for a strat_f16 step)
         cuda_fused = False
         if (fp16 or amp) and next(model.parameters()).is_cuda:
             from . import fused_network
@@ -101,13 +108,15 @@ class TrainHarness:
         if fp16 is True and cuda_fused and world == 1 and hasattr(self.opt, "step_grid_table") \
                 and getattr(model, "cuda_ray", False):
             self.fp16, self.amp_f16 = False, True
+        elif fp16 is True and cuda_fused and world == 1 and not getattr(model, "cuda_ray", False):
+            self.fp16, self.strat_f16 = False, True
         if amp == "bf16" and not fp16:
             if cuda_fused:
                 self.amp_bf16 = True            # (scoped to this harness's own steps: _amp_scope)
             else:
                 raise ValueError("amp='bf16' needs a CUDA model the fused path serves (network.py / network_ff.py nets)")
-        self.scaler = (torch.amp.GradScaler("cuda", enabled=self.fp16 or self.amp_f16)
-                       if (self.fp16 or self.amp_bf16 or self.amp_f16) else None)
+        self.scaler = (torch.amp.GradScaler("cuda", enabled=self.fp16 or self.amp_f16 or self.strat_f16)
+                       if (self.fp16 or self.amp_bf16 or self.amp_f16 or self.strat_f16) else None)
         self._amp_words = None
         if self.amp_f16:
             self.scaler._lazy_init_scale_growth_tracker(dev0)
@@ -150,8 +159,27 @@ class TrainHarness:
         harness's step, restored after it (the model keeps its own arithmetic for inference and for other harnesses)."""
         m = self.model
         prev = m.__dict__.get("mlp_precision", _UNSET)
-        m.mlp_precision = 3 if self.amp_f16 else 2
+        m.mlp_precision = 3 if (self.amp_f16 or self.strat_f16) else 2
         return prev
+
+    def _strat_f16_step(self, fn, native, *args):
+        """strat_f16: one step on the host GradScaler protocol under mlp32 precision 3 -- without autocast when the
+        stratified route serves it (`native`), under autocast (the statement) otherwise."""
+        prev = self._amp_scope()
+        self.fp16, self._f16_autocast = True, not native
+        try:
+            return fn(*args)
+        finally:
+            self.fp16, self._f16_autocast = False, True
+            self._amp_restore(prev)
+
+    def _strat_f16_ok(self, rays_o, rays_d, render_kw=None, bg_color=None):
+        """The stratified route takes this step's renders in the fp16 regime (decided per step: an averager may be
+        attached after __init__, and render keywords may ask for upsampling -- NeRFRenderer.run's default does)."""
+        from . import stratified
+        kw = render_kw or {}
+        return self.avg is None and stratified.supported(self.model, rays_o, rays_d, kw.get("upsample_steps", 128),
+                                                         bg_color, kw.get("out_dim_color"))
 
     def amp_skipped_steps(self):
         """fp16 closed form: optimizer steps the loss scaling has skipped so far (their gradients were not finite) -- the
@@ -865,7 +893,10 @@ class TrainHarness:
 
     def step_rgb(self, rays_o, rays_d, target, next_rays=None, **render_kw):
         """One RGB training step (nerf/utils.py:575-640 train_step + the optimizer part of train_one_epoch)."""
-        if self.amp_bf16 or self.amp_f16:
+        if self.strat_f16:
+            loss = self._strat_f16_step(lambda: self._step_rgb(rays_o, rays_d, target, next_rays, **render_kw),
+                                        self._strat_f16_ok(rays_o, rays_d, render_kw))
+        elif self.amp_bf16 or self.amp_f16:
             prev = self._amp_scope()
             try:
                 if self.amp_f16 and self._amp_closed_form_ok() and self._manual_ok(rays_o, rays_d, target, render_kw):
@@ -908,7 +939,7 @@ class TrainHarness:
             return self._replay(self._graphs[key], (rays_o, rays_d, target), 1)
         if self.fp16:
             self.opt.zero_grad(set_to_none=True)
-            with torch.autocast("cuda", dtype=torch.float16):
+            with torch.autocast("cuda", dtype=torch.float16, enabled=self._f16_autocast):
                 out = self.model.render(rays_o, rays_d, staged=False, bg_color=None, perturb=self.perturb, **render_kw)
                 loss = torch.nn.functional.mse_loss(out["image"], target)
             self.scaler.scale(loss).backward()
@@ -938,7 +969,14 @@ class TrainHarness:
 
     def step_events(self, data, opt, next_data=None):
         """One event training step: two renders sharing one backward (nerf/utils.py:482-573)."""
-        if self.amp_bf16 or self.amp_f16:
+        if self.strat_f16:
+            # (events.train_step_events: both renders take a [B,1,C] background drawn on the device)
+            bg = torch.empty((data["images"].shape[0], 1, opt.out_dim_color), device=data["rays_evs_o1"].device)
+            kw = dict(opt.render_kwargs, out_dim_color=opt.render_kwargs.get("out_dim_color", opt.out_dim_color))
+            native = (opt.event_only and self._strat_f16_ok(data["rays_evs_o1"], data["rays_evs_d1"], kw, bg)
+                      and self._strat_f16_ok(data["rays_evs_o2"], data["rays_evs_d2"], kw, bg))
+            loss = self._strat_f16_step(lambda: self._step_events(data, opt, next_data), native)
+        elif self.amp_bf16 or self.amp_f16:
             prev = self._amp_scope()
             try:
                 if self.amp_f16 and self._amp_closed_form_ok() and opt.event_only and self._events_manual_ok(data, opt):
@@ -984,7 +1022,7 @@ class TrainHarness:
         if self.fp16:
             # the shipped configs' fp16 = True around the event step (nerf/utils.py:964-975): autocast + GradScaler
             self.opt.zero_grad(set_to_none=True)
-            with torch.autocast("cuda", dtype=torch.float16):
+            with torch.autocast("cuda", dtype=torch.float16, enabled=self._f16_autocast):
                 loss, _ = train_step_events(self.model, data, opt)
             self.scaler.scale(loss).backward()
             self.scaler.unscale_(self.opt)

@@ -52,8 +52,10 @@ const char* enerf_last_error(void);
  * the library returns it (csrc/runtime.hip), enerf_amd/_lib.py parses it and refuses a library that answers differently,
  * __graft_entry__.build() and tests/test_abi.py compare against the parsed value.
  * 2: enerf_train_step_args lost its RCCL-tail fields, enerf_dp_* retired, enerf_nerf_mlp_* added.
- * 3: enerf_stratified_* added (the stratified sampler of NeRFRenderer.run). */
-#define ENERF_ABI_VERSION 3
+ * 3: enerf_stratified_* added (the stratified sampler of NeRFRenderer.run).
+ * 4: enerf_stratified_*_ex (fp16 storage of the colour rows / rgb / d rgb / dx) and enerf_mlp32_io16 (16-bit I/O of the
+ *    enerf_mlp32_*_p calls) added: the stratified sampler's fp16 regime. */
+#define ENERF_ABI_VERSION 4
 int enerf_abi_version(void);
 /* The library keeps grow-only scratch buffers per device (march chunk log, grid-backward record lists, ...).  Growing one
  * frees the old allocation; the counter returned here moves every time that happens.  A caller that captured library
@@ -497,6 +499,14 @@ int enerf_mlp32_valid_rows(const int32_t* device_count);
 /* The same with real rows = base + min(*device_count, cap): two renders' samples as one batch (the first render's M rows,
  * its padding included, then the second's counter capped at its own M).  cap == 0: as enerf_mlp32_valid_rows. */
 int enerf_mlp32_valid_rows_ex(const int32_t* device_count, uint32_t base, uint32_t cap);
+/* 1: the enerf_mlp32_forward_p / _backward_p calls that follow, until set again, take 16-bit (IEEE half) row-major
+ * tensors where they otherwise take fp32 ones: X [B,32], Y [B,y_stride], dY [B,dy_stride], y_sigmoid [B,y_sigmoid_stride]
+ * and dX [B,32]; weights, weight gradients, dsigma and h0 stay fp32.  Served with enerf_mlp32_precision(3) only, for
+ * two or three hidden layers, out_dim <= 16, x_layout 0 and no SH / density epilogue; the backward recomputes the hidden
+ * activations (fb is not read).  Outputs are the 16-bit values mode 3 rounds them to (a sigmoid output: sigmoid of the
+ * half-rounded net output, rounded to half).  Honours enerf_mlp32_valid_rows.  Returns the previous setting; < 0 only
+ * queries. */
+int enerf_mlp32_io16(int on);
 /* Arithmetic of the enerf_mlp32_* kernels (the nn.Linear nets of nerf/network.py:40-77 are fp32):
  *   0  v_mfma_f32_32x32x2_f32: every dot product an fp32 fmaf chain, bit-comparable with an fp32 GEMM;
  *   1  (default) split-bf16: every fp32 operand as bf16 hi + lo, three bf16 MFMA products per fp32 product (hi*hi +
@@ -850,6 +860,25 @@ int enerf_stratified_composite_backward(const float* g_image, const float* g_dep
  * dsigma * exp(clamp(h0, -15, 15))). */
 int enerf_stratified_scatter_geo_grad(const float* w, const int32_t* incl, const int32_t* count, const float* dx,
                                       uint32_t N, uint32_t T, float* dh16, enerf_stream_t stream);
+/* The same four with the storage of cin / rgb / g_rgb / dx chosen by `storage`: ENERF_F32 (the forms above) or ENERF_F16
+ * (the fp16 regime: cin [cap,32] and dx [cap,32] half, 64 B per row; rgb and g_rgb [cap,C] half; g_rgb = g_image * w
+ * rounded to half).  In ENERF_F16 the directions are rounded to half before the SH basis, which is evaluated in fp32 on
+ * them and stored as half (enerf_sh_encode_forward's ENERF_F16 values).  Everything else stays fp32. */
+int enerf_stratified_color_input_ex(const float* w, const int32_t* incl, const int32_t* count, const float* h16,
+                                    const float* rays_d, uint32_t N, uint32_t T, uint32_t cap, void* cin, uint32_t storage,
+                                    enerf_stream_t stream);
+int enerf_stratified_composite_forward_ex(const float* w, const int32_t* incl, const int32_t* count,
+                                          const float* opacity, const void* rgb, const float* bg, uint32_t bg_per_ray,
+                                          uint32_t N, uint32_t T, uint32_t C, float* image, uint32_t storage,
+                                          enerf_stream_t stream);
+int enerf_stratified_composite_backward_ex(const float* g_image, const float* g_depth, const float* z, const float* sigma,
+                                           const float* w, const float* nears, const float* fars, const int32_t* incl,
+                                           const int32_t* count, const void* rgb, const float* bg, uint32_t bg_per_ray,
+                                           uint32_t N, uint32_t T, uint32_t C, float inv_T, float density_scale,
+                                           uint32_t cap, float* g_sigma, void* g_rgb, uint32_t storage,
+                                           enerf_stream_t stream);
+int enerf_stratified_scatter_geo_grad_ex(const float* w, const int32_t* incl, const int32_t* count, const void* dx,
+                                         uint32_t N, uint32_t T, float* dh16, uint32_t storage, enerf_stream_t stream);
 
 #ifdef __cplusplus
 }

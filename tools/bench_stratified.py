@@ -10,8 +10,15 @@ Every window: `--warmup` untimed steps, a device synchronisation, then `--steps`
 one JSON line per shape and arm (ms per step or frame, samples/s) and one per shape with the masked fraction and the
 largest output difference between the arms on the same inputs.
 
-    python tools/bench_stratified.py [--shapes event,rgb,frame] [--steps 10] [--warmup 3] [--windows 2]
+    python tools/bench_stratified.py [--shapes event,rgb,frame] [--steps 10] [--warmup 3] [--windows 2] [--fp16]
+
+--fp16: the `fp16 = True` regime, three arms per shape in rotating order: "native_f16" (the native route at
+mlp_precision 3 with its fp16 colour rows, GradScaler host protocol, no autocast), "autocast" (the statement under
+torch.autocast(float16) + GradScaler: what `fp16 = True` on a cuda_ray-off model ran before the native fp16 regime) and
+"native_f32" (the native route in the default arithmetic, for reference).  The comparison line gives the largest
+output difference between native_f16 and autocast.
 """
+import contextlib
 import argparse
 import json
 import os
@@ -76,9 +83,9 @@ class Event:
         data = self.batches[self.i % len(self.batches)]
         self.i += 1
         self.adam.zero_grad(set_to_none=True)
-        loss, _ = events.train_step_events(self.model, data, self.opt)
-        loss.backward()
-        self.adam.step()
+        with _autocast(self):
+            loss, _ = events.train_step_events(self.model, data, self.opt)
+        _backward_step(self, loss)
 
 
 class Rgb:
@@ -106,11 +113,11 @@ class Rgb:
         ro, rd, target = self.batches[self.i % len(self.batches)]
         self.i += 1
         self.adam.zero_grad(set_to_none=True)
-        out = self.model.render(ro, rd, staged=False, bg_color=None, perturb=True, num_steps=T, upsample_steps=0,
-                                out_dim_color=3)
-        loss = ((out["image"] - target) ** 2).mean()
-        loss.backward()
-        self.adam.step()
+        with _autocast(self):
+            out = self.model.render(ro, rd, staged=False, bg_color=None, perturb=True, num_steps=T, upsample_steps=0,
+                                    out_dim_color=3)
+            loss = ((out["image"] - target) ** 2).mean()
+        _backward_step(self, loss)
 
 
 class Frame:
@@ -128,15 +135,52 @@ class Frame:
         return [out["image"], out["depth"]]
 
     def step(self):
-        self.outputs(self.model)
+        with _autocast(self):
+            self.outputs(self.model)
+
+
+def _autocast(shape):
+    return torch.autocast("cuda", dtype=torch.float16) if getattr(shape, "autocast", False) else contextlib.nullcontext()
+
+
+def _backward_step(shape, loss):
+    """plain backward + Adam, or the GradScaler's host protocol in the fp16 arms (scale, backward, step, update)"""
+    sc = getattr(shape, "scaler", None)
+    if sc is None:
+        loss.backward()
+        shape.adam.step()
+        return
+    sc.scale(loss).backward()
+    sc.step(shape.adam)
+    sc.update()
 
 
 def _set(on):
     stratified.ENABLED = on
 
 
-def _window(shape, on, steps, warmup):
-    _set(on)
+def _set_arm(shape, arm):
+    """--fp16 arms: native_f16 / autocast / native_f32 (see the module docstring)"""
+    _set(arm != "autocast")
+    if arm == "native_f16":
+        shape.model.mlp_precision = 3
+    else:
+        shape.model.__dict__.pop("mlp_precision", None)
+    shape.autocast = arm == "autocast"
+    if hasattr(shape, "adam"):
+        if arm == "native_f32":
+            shape.scaler = None
+        else:
+            if getattr(shape, "_scaler", None) is None:
+                shape._scaler = torch.amp.GradScaler("cuda")
+            shape.scaler = shape._scaler
+
+
+def _window(shape, on, steps, warmup, arm=None):
+    if arm is None:
+        _set(on)
+    else:
+        _set_arm(shape, arm)
     calls = stratified.stats["calls"]
     for _ in range(warmup):
         shape.step()
@@ -168,14 +212,65 @@ def _compare(shape):
     return masked, diff
 
 
+def _compare_fp16(shape):
+    """native_f16 vs autocast on the same model, inputs and random draws: largest |difference|, masked fraction"""
+    stratified.KEEP_LAST = True
+    _set_arm(shape, "native_f16")
+    with _autocast(shape):
+        got = [x.detach().float() for x in shape.outputs(shape.model)]
+    last = stratified.last
+    masked = float(last["count"].sum().item()) / float(last["w"].numel())
+    stratified.KEEP_LAST = False
+    stratified.last = None
+    _set_arm(shape, "autocast")
+    with _autocast(shape):
+        ref = [x.detach().float() for x in shape.outputs(shape.model)]
+    diff = max(float((g - r).abs().nan_to_num(0.0).max().item()) for g, r in zip(got, ref))
+    return masked, diff
+
+
+def main_fp16(a, classes):
+    arms = a.arms.split(",")
+    for name in a.shapes.split(","):
+        shape = classes[name]()
+        masked, diff = _compare_fp16(shape)
+        steps = max(1, a.steps // 4) if name == "frame" else a.steps
+        times = {arm: [] for arm in arms}
+        for w in range(a.windows):
+            order = arms[w % len(arms):] + arms[:w % len(arms)]
+            for arm in order:
+                times[arm].append(_window(shape, arm != "autocast", steps, a.warmup if name != "frame" else 1, arm))
+        samples = shape.rays * shape.renders * T
+        res = {}
+        for arm in arms:
+            ms = float(np.median(times[arm]))
+            res[arm] = ms
+            print(json.dumps({"shape": name, "arm": arm, "ms": round(ms, 3),
+                              "windows_ms": [round(x, 3) for x in times[arm]], "samples_per_step": samples,
+                              "samples_per_s": round(samples / ms * 1e3, 1)}), flush=True)
+        line = {"shape": name, "masked_fraction": round(masked, 5), "max_abs_diff_f16_vs_autocast": diff}
+        if "native_f16" in res and "autocast" in res:
+            line["speedup_f16_over_autocast"] = round(res["autocast"] / res["native_f16"], 3)
+        if "native_f16" in res and "native_f32" in res:
+            line["speedup_f16_over_f32"] = round(res["native_f32"] / res["native_f16"], 3)
+        print(json.dumps(line), flush=True)
+        del shape
+        torch.cuda.empty_cache()
+    _set(True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--shapes", default="event,rgb,frame")
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--windows", type=int, default=2)
+    ap.add_argument("--fp16", action="store_true")
+    ap.add_argument("--arms", default="native_f16,autocast,native_f32", help="--fp16: arms to time (profiling: one)")
     a = ap.parse_args()
     classes = {"event": Event, "rgb": Rgb, "frame": Frame}
+    if a.fp16:
+        return main_fp16(a, classes)
     for name in a.shapes.split(","):
         shape = classes[name]()
         masked, diff = _compare(shape)
