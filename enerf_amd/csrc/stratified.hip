@@ -53,7 +53,12 @@ __device__ __forceinline__ float clamp01(float x) { return (x != x) ? x : (x < 0
 __device__ __forceinline__ float ld_e(const float* p) { return *p; }
 __device__ __forceinline__ float ld_e(const __half* p) { return __half2float(*p); }
 __device__ __forceinline__ void st_e(float* p, float v) { *p = v; }
-__device__ __forceinline__ void st_e(__half* p, float v) { *p = __float2half(v); }
+// (the empty asm keeps v an fp32 value: without it the compiler folds a product and this conversion into one
+//  v_fma_mixlo_f16, a single rounding of the exact product, which differs from torch's fp32-then-fp16 at fp16 ties)
+__device__ __forceinline__ void st_e(__half* p, float v) {
+    asm volatile("" : "+v"(v));
+    *p = __float2half(v);
+}
 __device__ __forceinline__ uint32_t pack2h(float a, float b) {
     return (uint32_t)__half_as_ushort(__float2half(a)) | ((uint32_t)__half_as_ushort(__float2half(b)) << 16);
 }

@@ -194,7 +194,20 @@ def _close_rel(a, b, rel, what):
 @pytest.mark.parametrize("bg_form", ["none", "shared", "per_ray"])
 @pytest.mark.parametrize("C", [1, 3])
 def test_route_on_vs_off(C, bg_form):
-    N, T = 4096, 512
+    _on_vs_off(C, bg_form, 512)
+
+
+@pytest.mark.parametrize("T", [1100])
+@pytest.mark.parametrize("bg_form", ["none", "shared", "per_ray"])
+@pytest.mark.parametrize("C", [1, 3])
+def test_route_on_vs_off_beyond_one_pass(C, bg_form, T):
+    """The same at more than one scan pass per ray (64 lanes x 8 samples = 512): the carried product, the T_k kept in
+    g_sigma between the backward's sweeps, the recount of earlier passes' rows and the reverse carry all run."""
+    _on_vs_off(C, bg_form, T)
+
+
+def _on_vs_off(C, bg_form, T):
+    N = 4096
     model = _scene(C).to(DEV).train()
     o1, d1 = _hit_rays(N - 512, 11)
     o2, d2 = _empty_rays(512, 12)
@@ -242,6 +255,63 @@ def _mask_flips(model, ro, rd, T, w):
         w_ref, _ = sampler.ray_weights(z, sigma, width, model.density_scale)
     assert (w - w_ref).abs().max().item() < 1e-6
     return ((w > 1e-4) != (w_ref > 1e-4)).any(dim=1)
+
+
+@contextlib.contextmanager
+def _nan_buffers():
+    """The route's uninitialised buffers (stratified.py's torch.empty) come NaN-filled -- what a freed NaN block of the
+    caching allocator hands out, on every allocation: a pad row the kernels fail to zero shows up as a NaN gradient."""
+    import types
+    from enerf_amd import stratified
+
+    class _Torch(types.ModuleType):
+        def __getattr__(self, name):
+            return getattr(torch, name)
+
+    def empty(*shape, **kw):
+        t = torch.empty(*shape, **kw)
+        return t.fill_(float("nan")) if t.is_floating_point() else t
+
+    proxy = _Torch("torch")
+    proxy.empty = empty
+    prev = stratified.torch
+    stratified.torch = proxy
+    try:
+        yield
+    finally:
+        stratified.torch = prev
+
+
+@pytest.mark.parametrize("kind", ["every_sample_masked", "partly_masked"])
+def test_pad_rows_with_nan_filled_buffers(kind):
+    """N*T not a multiple of 32.  Every sample masked (low uniform density: the compact list is as long as its capacity,
+    total == cap) or some (the list ends inside a 32-row tile whose pad rows the MLP kernels process as real rows: the
+    colour rows and d rgb there must be zero).  Every buffer the route leaves for its kernels to fill starts as NaN; the
+    gradients must be finite and those of the statement."""
+    C = 3
+    N, T = (3, 24) if kind == "every_sample_masked" else (5, 24)
+    model = _scene(C).to(DEV).train()
+    if kind == "every_sample_masked":
+        with torch.no_grad():
+            model.encoder.embeddings.zero_()                  # features 0 -> h0 = 0 -> sigma = 1 everywhere
+    o, d = _hit_rays(N, 31)
+    ro, rd = o.to(DEV)[None], d.to(DEV)[None]
+    bg = torch.full((C,), 0.4, device=DEV)
+    img0, dep0, gr0, _ = _arm(model, ro, rd, T, bg, False)
+    with _nan_buffers():
+        img1, dep1, gr1, last = _arm(model, ro, rd, T, bg, True)
+    total = int(last["incl"][-1].item())
+    if kind == "every_sample_masked":
+        assert total == N * T and (N * T) % 32 != 0
+    else:
+        assert 0 < total < N * T and total % 32 != 0, total
+    assert not _mask_flips(model, ro, rd, T, last["w"]).any()
+    for n in gr1:
+        assert torch.isfinite(gr1[n]).all(), n
+    assert_close(img1, img0, rtol=0, atol=1e-5)
+    assert_close(dep1, dep0, rtol=0, atol=1e-5)
+    for n in gr0:
+        _close_rel(gr1[n], gr0[n], 1e-4, n)
 
 
 def test_batch_without_masked_samples():

@@ -158,7 +158,19 @@ def test_against_the_regime_restated_by_the_statement(C, bound, monkeypatch):
     GEMM library), which moves a rounded fp16 value by one ulp now and then.
     Observed on an MI355X (max over the four cases): image 1.05e-4 abs, depth 5.4e-6 abs, worst parameter gradient
     9.6e-4 relative L2 (the hash table's; the MLP weights' stay near 2.5e-4).  Bars: just under 4x those."""
-    N, T = 4096, 128
+    _restated(C, bound, 128, monkeypatch)
+
+
+@pytest.mark.parametrize("T", [1100])
+@pytest.mark.parametrize("bound", [2, 3])
+@pytest.mark.parametrize("C", [1, 3])
+def test_against_the_regime_restated_by_the_statement_beyond_one_pass(C, bound, T, monkeypatch):
+    """The same comparison at more than one scan pass per ray (64 lanes x 8 samples = 512), same bars."""
+    _restated(C, bound, T, monkeypatch)
+
+
+def _restated(C, bound, T, monkeypatch):
+    N = 4096
     model = _model(C, bound, 9).train()
     ro, rd = _hit_rays(N, 13 + bound, bound)
     bg = torch.rand(N, C, device=DEV)
