@@ -141,6 +141,10 @@ SIGNATURES = {
     "enerf_stratified_composite_backward_ex": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _u32, _u32, _u32,
                                                _u32, _f32, _f32, _u32, _vp, _vp, _u32, _vp],
     "enerf_stratified_scatter_geo_grad_ex": [_vp, _vp, _vp, _vp, _u32, _u32, _vp, _u32, _vp],
+    "enerf_mesh_lattice": [_vp, _u32, _u32, _u32, _vp, _vp],
+    "enerf_marching_cubes_workspace": [_u32, _c.POINTER(_c.c_uint64)],
+    "enerf_marching_cubes_count": [_vp, _u32, _c.c_double, _vp, _vp, _vp],
+    "enerf_marching_cubes_emit": [_vp, _u32, _c.c_double, _vp, _c.c_uint64, _c.c_uint64, _vp, _vp, _vp],
 }
 
 F32, F16, BF16 = 0, 1, 2

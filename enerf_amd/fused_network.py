@@ -420,20 +420,25 @@ def _sigma_only(net, feats, sigma, B):
                                               sigma.data_ptr(), None, L.stream_handle()), "mlp32_forward_p(sigma only)")
 
 
-def density_sigma(net, x):
+def density_sigma(net, x, out=None, feats=None):
     """sigma [N] only (no geo_feat, no autograd): what update_extra_state needs from density() for its 2 M cell
-    samples per cascade -- the sigma MLP writes exp(column 0) and nothing else."""
+    samples per cascade -- the sigma MLP writes exp(column 0) and nothing else.  `out`: a contiguous fp32 [N] to write
+    sigma into; `feats`: a flat fp32 buffer of at least 16 * pad32(N) * 2 for the features, in place of the model's
+    `_density_scratch` (mesh.density_field: a call that must leave nothing behind)."""
     enc = net.encoder
     x = x.contiguous()
     B = x.shape[0]
     dev = x.device
-    sigma = torch.empty(B, dtype=torch.float32, device=dev)      # (the caller's to keep; the features are scratch)
+    sigma = torch.empty(B, dtype=torch.float32, device=dev) if out is None else out   # (the caller's to keep)
     if B == 0:
         return sigma
     Bp = pad32(B)
     S = float(np.log2(enc.per_level_scale))
     affine = (float(net.bound), float(np.float32(1.0) / np.float32(2 * net.bound)))
-    feats = _density_scratch(net, "feats", (16, Bp, 2), torch.float32, dev)
+    if feats is None:
+        feats = _density_scratch(net, "feats", (16, Bp, 2), torch.float32, dev)
+    else:
+        feats = feats[:16 * Bp * 2].view(16, Bp, 2)
     _gb.grid_encode_forward(x, enc.embeddings.detach().contiguous(), enc.offsets, feats, B, 3, 2, 16, S,
                             enc.base_resolution, False, feats, enc.gridtype_id, layout=2, affine=affine)
     _sigma_only(net, feats, sigma, B)

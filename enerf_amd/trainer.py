@@ -230,6 +230,13 @@ class TrainHarness:
         from .checkpoint import save_checkpoint
         return save_checkpoint(self, path, full=full)
 
+    def save_mesh(self, save_path, resolution=256, threshold=10):
+        """The reference's Trainer.save_mesh (nerf/utils.py:712-732): sigma on a resolution^3 lattice over aabb_infer,
+        marching cubes at `threshold`, a binary PLY at `save_path` (rank 0 writes).  The query runs in this harness's
+        regime, as the reference's autocast(enabled=fp16) does.  -> (vertices [V, 3] fp64 world, triangles [F, 3] int32)."""
+        from .mesh import harness_save_mesh
+        return harness_save_mesh(self, save_path, resolution, threshold)
+
     def load_checkpoint(self, checkpoint, model_only=False):
         """Resume from a checkpoint in the reference's format (nerf/utils.py:1353-1415), whoever wrote it."""
         from .checkpoint import load_checkpoint

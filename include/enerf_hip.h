@@ -54,8 +54,9 @@ const char* enerf_last_error(void);
  * 2: enerf_train_step_args lost its RCCL-tail fields, enerf_dp_* retired, enerf_nerf_mlp_* added.
  * 3: enerf_stratified_* added (the stratified sampler of NeRFRenderer.run).
  * 4: enerf_stratified_*_ex (fp16 storage of the colour rows / rgb / d rgb / dx) and enerf_mlp32_io16 (16-bit I/O of the
- *    enerf_mlp32_*_p calls) added: the stratified sampler's fp16 regime. */
-#define ENERF_ABI_VERSION 4
+ *    enerf_mlp32_*_p calls) added: the stratified sampler's fp16 regime.
+ * 5: enerf_mesh_lattice and enerf_marching_cubes_* added (mesh export, Trainer.save_mesh). */
+#define ENERF_ABI_VERSION 5
 int enerf_abi_version(void);
 /* The library keeps grow-only scratch buffers per device (march chunk log, grid-backward record lists, ...).  Growing one
  * frees the old allocation; the counter returned here moves every time that happens.  A caller that captured library
@@ -879,6 +880,24 @@ int enerf_stratified_composite_backward_ex(const float* g_image, const float* g_
                                            enerf_stream_t stream);
 int enerf_stratified_scatter_geo_grad_ex(const float* w, const int32_t* incl, const int32_t* count, const void* dx,
                                          uint32_t N, uint32_t T, float* dh16, uint32_t storage, enerf_stream_t stream);
+
+/* ------------------------------------------------------------------ mesh export
+ * Trainer.save_mesh (nerf/utils.py:219-249, 712-732), csrc/mesh.hip; semantics in enerf_amd/mesh.py and DESIGN.md 4.10.
+ * R (lattice points per axis) must be 2 .. 512.  The field u [R,R,R] is fp32, x slowest.
+ *
+ * lattice: the points of x-planes [x0, x0 + nx) in field order, pts [nx*R*R, 3] fp32.  box [host]: lo[3], hi[3], step[3]
+ * with step = (hi - lo) / (R - 1) in fp32; coordinate i = fmaf(i, step, lo) for i < R / 2, else
+ * fmaf(-(R - 1 - i), step, hi): torch.linspace(lo, hi, R) on the CPU, bit for bit. */
+int enerf_mesh_lattice(const float* box, uint32_t R, uint32_t x0, uint32_t nx, float* pts, enerf_stream_t stream);
+/* Marching cubes in two calls around one read-back.  workspace: bytes of `ws` for R [host ptr].  count: classifies every
+ * point and cell and scans the counts; totals [3] int64 (device) = vertices, triangles, non-finite values of u.  emit (the
+ * same u, threshold and ws, V and F as counted; nothing is written when u held a non-finite value and the caller stopped):
+ * verts [V,3] fp64 in index space, tris [F,3] int32, in the order and with the table of mc_tables.h. */
+int enerf_marching_cubes_workspace(uint32_t R, uint64_t* bytes);
+int enerf_marching_cubes_count(const float* u, uint32_t R, double threshold, void* ws, int64_t* totals,
+                               enerf_stream_t stream);
+int enerf_marching_cubes_emit(const float* u, uint32_t R, double threshold, void* ws, uint64_t V, uint64_t F,
+                              double* verts, int32_t* tris, enerf_stream_t stream);
 
 #ifdef __cplusplus
 }
