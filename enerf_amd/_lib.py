@@ -80,6 +80,8 @@ SIGNATURES = {
                              _u32, _vp],
     "enerf_sh_encode_forward_strided": [_vp, _vp, _u32, _u32, _u32, _vp],
     "enerf_debug_grid_level_mask": [_u32],
+    "enerf_debug_sweep_route": [_u32, _u32],
+    "enerf_debug_sweep_schedule": [_u32, _u32, _u32, _vp, _u32],
     "enerf_debug_mlp32_wgrad_blocks": [_u32],
     "enerf_debug_mlp32_grid_caps": [_u32, _u32],
     "enerf_debug_march_wave_max_rays": [_u32],

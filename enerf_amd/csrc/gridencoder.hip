@@ -27,6 +27,7 @@
 #include <math.h>
 
 #include <type_traits>
+#include <utility>
 
 #include "common.h"
 #include "sweep_points.h"
@@ -477,6 +478,205 @@ __global__ void __launch_bounds__(kPtsPerBlock) k_grid_fwd(const float* __restri
     }
     grid_fwd_block<T, D, C>(blockIdx.x - carry_blocks, inputs, grid, offsets, outputs, B, L, tab, calc_grad_inputs, dy_dx,
                             gridtype, out_layout, nchunks, gen);
+}
+
+// The feature of one point at one level, grid_fwd_block's sequence: cell, weights, the 2^D corner gathers accumulated in
+// corner order (`in`: the point in [0, 1]^D).  The sweep's two workgroup flavours share it, so a point's feature has the
+// same bits whichever of them computed it -- and the same as the training forward's (tests/test_gpu_sweep_schedule.py).
+template <typename T, int D, int C>
+__device__ __forceinline__ Feat<T, C> interp_level(const float (&in)[D], float scale, const LevelGeom<D>& geom,
+                                                   const Feat<T, C>* __restrict__ rows, float (&pos)[D],
+                                                   uint32_t (&pos_grid)[D]) {
+#pragma unroll
+    for (int d = 0; d < D; d++) {
+        pos[d] = fmaf(in[d], scale, 0.5f);
+        const float fl = floorf(pos[d]);
+        pos_grid[d] = (uint32_t)fl;
+        pos[d] -= (float)pos_grid[d];
+    }
+
+    // issue all gathers before using any of them
+    Feat<T, C> f[1 << D];
+    float w[1 << D];
+#pragma unroll
+    for (int idx = 0; idx < (1 << D); idx++) {
+        float wi = 1;
+#pragma unroll
+        for (int d = 0; d < D; d++) wi *= (idx & (1 << d)) ? pos[d] : 1 - pos[d];
+        w[idx] = wi;
+    }
+    if constexpr (2 * sizeof(Feat<T, C>) <= 16) {
+        // corners 2k (x) and 2k+1 (x+1): one double-width load when their rows are adjacent, else the aligned pair
+        // holding the first row plus a single-row load of the second (hashed levels, odd x).  hashmap_size is a
+        // multiple of 8, so the aligned pair never leaves the level.
+        constexpr int H = 1 << (D - 1);
+        uint32_t cr[1 << D], r0[H], r1[H];
+        corner_rows<D>(geom, pos_grid, cr);
+        bool adj[H];
+        FeatPair<T, C> q[H];
+#pragma unroll
+        for (int k = 0; k < H; k++) {
+            r0[k] = cr[2 * k];
+            r1[k] = cr[2 * k + 1];
+            adj[k] = ((r0[k] ^ r1[k]) == 1u) || (r1[k] == r0[k] + 1u);
+            const uint32_t lo = r0[k] < r1[k] ? r0[k] : r1[k];
+            q[k] = *reinterpret_cast<const FeatPair<T, C>*>(rows + (adj[k] ? lo : (r0[k] & ~1u)));
+        }
+        Feat<T, C> e[H];
+#pragma unroll
+        for (int k = 0; k < H; k++) {
+#pragma unroll
+            for (int c = 0; c < C; c++) e[k].v[c] = from_f<T>(0.0f);
+            if (!adj[k]) e[k] = rows[r1[k]];
+        }
+#pragma unroll
+        for (int k = 0; k < H; k++) {
+            const bool first = adj[k] ? (r0[k] < r1[k]) : ((r0[k] & 1u) == 0u);
+#pragma unroll
+            for (int c = 0; c < C; c++) {
+                f[2 * k].v[c] = first ? q[k].a.v[c] : q[k].b.v[c];
+                f[2 * k + 1].v[c] = adj[k] ? (first ? q[k].b.v[c] : q[k].a.v[c]) : e[k].v[c];
+            }
+        }
+    } else {
+        uint32_t cr[1 << D];
+        corner_rows<D>(geom, pos_grid, cr);
+#pragma unroll
+        for (int idx = 0; idx < (1 << D); idx++) f[idx] = rows[cr[idx]];
+    }
+    float res[C];
+#pragma unroll
+    for (int c = 0; c < C; c++) res[c] = 0;
+#pragma unroll
+    for (int idx = 0; idx < (1 << D); idx++) {
+#pragma unroll
+        for (int c = 0; c < C; c++) res[c] = acc_feat(res[c], w[idx], f[idx].v[c]);
+    }
+    Feat<T, C> o;
+#pragma unroll
+    for (int c = 0; c < C; c++) o.v[c] = from_f<T>(res[c]);
+    return o;
+}
+
+// point b of a full sweep at one level: generated, encoded, written in `out_layout` -- grid_fwd_block's sequence for a
+// sweep (no input gradient)
+template <int C>
+__device__ __forceinline__ void sweep_level_point(uint32_t level, uint32_t b, const float* __restrict__ grid,
+                                                  const int32_t* __restrict__ offsets, float* __restrict__ outputs,
+                                                  uint32_t B, uint32_t L, const LevelTab& tab, uint32_t gridtype,
+                                                  int out_layout, const SweepGen& gen) {
+    const uint32_t Bp = (B + 31u) & ~31u;
+    Feat<float, C>* outs = reinterpret_cast<Feat<float, C>*>(outputs);
+    Feat<float, C> z;
+#pragma unroll
+    for (int c = 0; c < C; c++) z.v[c] = 0.0f;
+    if (b >= B) {
+        if (out_layout == 2 && b < Bp) outs[(size_t)level * Bp + b] = z;     // zeroed pad rows of the [L,Bp,C] layout
+        return;
+    }
+    float q[3], in[3];
+    sweep_point(gen, b, q);
+    bool oob = false;
+#pragma unroll
+    for (int d = 0; d < 3; d++) {
+        in[d] = (q[d] + tab.in_add) * tab.in_mul;
+        oob |= (in[d] < 0 || in[d] > 1);
+    }
+    Feat<float, C>* out = outs + (out_layout == 0 ? (size_t)level * B + b
+                                                  : out_layout == 1 ? (size_t)b * L + level : (size_t)level * Bp + b);
+    if (oob) {
+        *out = z;
+        return;
+    }
+    const uint32_t off0 = (uint32_t)offsets[level];
+    const LevelGeom<3> geom = make_geom<3>(gridtype, (uint32_t)offsets[level + 1] - off0, tab.resolution[level]);
+    float pos[3];
+    uint32_t pos_grid[3];
+    *out = interp_level<float, 3, C>(in, tab.scale[level], geom, reinterpret_cast<const Feat<float, C>*>(grid) + off0,
+                                     pos, pos_grid);
+}
+
+// ---- the full density-grid sweep (enerf_grid_encode_forward_sweep): a static schedule instead of the snake deal.
+// Units: every level from `walk` on, and the walker -- levels 0 .. walk-1 of a point by ONE thread, which generates the
+// point once instead of once per level (the generator is 120 of a dense level's ~276 vector instructions; the walked
+// tables, 1.8 MB for levels 0-3, share one L2).  The host (build_sweep_schedule) deals the units to the four XCD pairs
+// as (pair, unit, chunk range) segments so that every pair carries the same measured cost: whole units while they fit,
+// the rest split by point range.  A pair walks its segments in order, so each XCD still has one table at a time; the
+// two members take alternate chunks of the pair's list, as in decode_block_fwd.
+constexpr uint32_t kWalkUnit = 0x80000000u;
+constexpr uint32_t kMaxSweepSegs = 48;
+struct SweepSched {
+    uint32_t first[kGroups + 1];      // segments of pair g: [first[g], first[g + 1])
+    uint32_t unit[kMaxSweepSegs];     // level, or kWalkUnit
+    uint32_t chunk0[kMaxSweepSegs];   // first chunk of the segment in its unit's point range
+    uint32_t kend[kMaxSweepSegs];     // end of the segment in its pair's chunk list
+};
+
+// point b at levels 0 .. WALK-1 (those below L and in the level mask), the same interp_level sequence per level
+template <int C, int WALK>
+__device__ __forceinline__ void sweep_walk_point(uint32_t b, const float* __restrict__ grid,
+                                                 const int32_t* __restrict__ offsets, float* __restrict__ outputs,
+                                                 uint32_t B, uint32_t L, const LevelTab& tab, uint32_t gridtype,
+                                                 int out_layout, const SweepGen& gen) {
+    const uint32_t Bp = (B + 31u) & ~31u;
+    Feat<float, C> z;
+#pragma unroll
+    for (int c = 0; c < C; c++) z.v[c] = 0.0f;
+    Feat<float, C>* outs = reinterpret_cast<Feat<float, C>*>(outputs);
+    if (b >= B) {
+        if (out_layout == 2 && b < Bp) {     // zeroed pad rows of the [L,Bp,C] layout
+#pragma unroll
+            for (uint32_t level = 0; level < (uint32_t)WALK; level++)
+                if (level < L && level_enabled(tab, level)) outs[(size_t)level * Bp + b] = z;
+        }
+        return;
+    }
+    float q[3], in[3];
+    sweep_point(gen, b, q);
+    bool oob = false;
+#pragma unroll
+    for (int d = 0; d < 3; d++) {
+        in[d] = (q[d] + tab.in_add) * tab.in_mul;
+        oob |= (in[d] < 0 || in[d] > 1);
+    }
+#pragma unroll
+    for (uint32_t level = 0; level < (uint32_t)WALK; level++) {
+        if (level >= L || !level_enabled(tab, level)) continue;
+        Feat<float, C>* out = outs + (out_layout == 0 ? (size_t)level * B + b
+                                                      : out_layout == 1 ? (size_t)b * L + level : (size_t)level * Bp + b);
+        if (oob) {
+            *out = z;
+            continue;
+        }
+        const uint32_t off0 = (uint32_t)offsets[level];
+        const LevelGeom<3> geom = make_geom<3>(gridtype, (uint32_t)offsets[level + 1] - off0, tab.resolution[level]);
+        float pos[3];
+        uint32_t pos_grid[3];
+        *out = interp_level<float, 3, C>(in, tab.scale[level], geom,
+                                         reinterpret_cast<const Feat<float, C>*>(grid) + off0, pos, pos_grid);
+    }
+}
+
+template <int C, int WALK>
+__global__ void __launch_bounds__(kPtsPerBlock) k_grid_fwd_sweep(const float* __restrict__ grid,
+                                                                 const int32_t* __restrict__ offsets,
+                                                                 float* __restrict__ outputs, uint32_t B, uint32_t L,
+                                                                 LevelTab tab, uint32_t gridtype, int out_layout,
+                                                                 SweepGen gen, SweepSched sch) {
+    const uint32_t xcd = blockIdx.x & 7u, group = xcd / kGroupXcds;
+    const uint32_t k = (blockIdx.x >> 3) * kGroupXcds + xcd % kGroupXcds;     // place in the pair's chunk list
+    const uint32_t end = sch.first[group + 1];
+    uint32_t s = sch.first[group], kbeg = 0;
+    while (s < end && k >= sch.kend[s]) kbeg = sch.kend[s++];
+    if (s >= end) return;
+    const uint32_t b = (sch.chunk0[s] + (k - kbeg)) * kPtsPerBlock + threadIdx.x;
+    const uint32_t unit = sch.unit[s];
+    if (WALK > 0 && unit == kWalkUnit) {
+        sweep_walk_point<C, WALK>(b, grid, offsets, outputs, B, L, tab, gridtype, out_layout, gen);
+        return;
+    }
+    if (!level_enabled(tab, unit)) return;
+    sweep_level_point<C>(unit, b, grid, offsets, outputs, B, L, tab, gridtype, out_layout, gen);
 }
 
 template <int C>
@@ -1609,6 +1809,131 @@ int launch_fwd(const float* inputs, const T* emb, const int32_t* offsets, T* out
     return 0;
 }
 
+// Cost of each sweep unit on ONE XCD pair: us for the 6.29 M points of the bound-3 sweep (3 cascades, H = 128), each
+// level alone (tools/sweep_levels.py, profiles/r08_sweep_levels_before.txt); the walker of 4 / 5 levels alone
+// (tools/sweep_units.py, profiles/r08_sweep_units.txt).  Only their ratios matter; levels past 16 cost what level 15 does.
+const float kSweepLevelUs[16] = {264.2f, 256.0f, 258.0f, 264.2f, 259.3f, 273.3f, 277.9f, 328.9f,
+                                 394.1f, 501.5f, 591.6f, 655.3f, 683.6f, 697.8f, 700.1f, 704.0f};
+const float kSweepWalkUs[6] = {0.0f, 0.0f, 0.0f, 0.0f, 463.2f, 531.5f};      // [walked levels]
+uint32_t g_sweep_route = 0;        // enerf_debug_sweep_route: 0 = the schedule below, 1 = k_grid_fwd's snake deal
+uint32_t g_sweep_walk = 5;         // levels taken by the walker (0, 4 or 5)
+
+struct SweepSeg {
+    uint32_t group, unit, chunk0, n;
+};
+// The schedule of an L-level sweep of `nchunks` chunks per level: segments ordered by pair, then by when the pair runs
+// them.  Largest units first, each whole to the least-loaded pair while that stays within the mean; what is left is
+// poured by point range into the pairs furthest below it.  -> number of segments, or -1 when `cap` is too small.
+int build_sweep_schedule(uint32_t L, uint32_t walk, uint32_t nchunks, SweepSeg* segs, uint32_t cap) {
+    struct Unit {
+        uint32_t id;
+        double cost;
+    };
+    Unit units[kMaxLevels + 1];
+    uint32_t nu = 0;
+    const uint32_t walked = walk < L ? walk : L;
+    if (walked) units[nu++] = {kWalkUnit, (double)kSweepWalkUs[walk] * walked / walk};
+    for (uint32_t l = walked; l < L; l++) units[nu++] = {l, (double)kSweepLevelUs[l < 16 ? l : 15]};
+    // (stable by cost, the finer level first on a tie)
+    for (uint32_t i = 1; i < nu; i++)
+        for (uint32_t j = i; j > 0 && units[j].cost > units[j - 1].cost; j--) std::swap(units[j], units[j - 1]);
+    double total = 0.0;
+    for (uint32_t i = 0; i < nu; i++) total += units[i].cost;
+    const double target = total / kGroups;
+    double load[kGroups] = {};
+    SweepSeg raw[kMaxSweepSegs * 2];
+    uint32_t nraw = 0;
+    Unit pour[kMaxLevels + 1];
+    uint32_t np = 0;
+    for (uint32_t i = 0; i < nu; i++) {
+        uint32_t g = 0;
+        for (uint32_t h = 1; h < kGroups; h++)
+            if (load[h] < load[g]) g = h;
+        if (load[g] + units[i].cost <= target * (1.0 + 1e-6)) {
+            raw[nraw++] = {g, units[i].id, 0u, nchunks};
+            load[g] += units[i].cost;
+        } else {
+            pour[np++] = units[i];
+        }
+    }
+    for (uint32_t i = 0; i < np; i++) {
+        const double per_chunk = pour[i].cost / nchunks;
+        uint32_t c0 = 0;
+        while (c0 < nchunks) {
+            uint32_t g = 0;
+            for (uint32_t h = 1; h < kGroups; h++)
+                if (load[h] < load[g]) g = h;
+            const uint32_t left = nchunks - c0;
+            const double want = (target - load[g]) / per_chunk;
+            uint32_t n = want < 1.0 ? left : (uint32_t)fmin((double)left, floor(want + 0.5));
+            if (n == 0) n = 1;
+            if (left - n < 8u) n = left;           // (no slivers)
+            if (nraw == kMaxSweepSegs * 2) return -1;
+            raw[nraw++] = {g, pour[i].id, c0, n};
+            load[g] += n * per_chunk;
+            c0 += n;
+        }
+    }
+    uint32_t ns = 0;
+    for (uint32_t g = 0; g < kGroups; g++)
+        for (uint32_t i = 0; i < nraw; i++) {
+            if (raw[i].group != g) continue;
+            if (ns == cap) return -1;
+            segs[ns++] = raw[i];
+        }
+    return (int)ns;
+}
+
+int launch_sweep(const float* emb, const int32_t* offsets, float* outputs, uint32_t B, uint32_t C, uint32_t L,
+                 const LevelTab& tab, uint32_t gridtype, int layout, const SweepGen& gen, hipStream_t s,
+                 hipEvent_t ev_start, hipEvent_t ev_stop) {
+    const uint32_t nchunks = div_up(layout == 2 ? ((B + 31u) & ~31u) : B, kPtsPerBlock);
+    const uint32_t walk = g_sweep_walk;
+    SweepSeg segs[kMaxSweepSegs];
+    const int ns = build_sweep_schedule(L, walk, nchunks, segs, kMaxSweepSegs);
+    if (ns < 0) ENERF_BADARG("grid_encode_forward_sweep: no schedule of %u levels within %u segments", L, kMaxSweepSegs);
+    SweepSched sch{};
+    uint32_t most = 0;
+    for (uint32_t g = 0, i = 0; g < kGroups; g++) {
+        sch.first[g] = i;
+        uint32_t k = 0;
+        for (; i < (uint32_t)ns && segs[i].group == g; i++) {
+            sch.unit[i] = segs[i].unit;
+            sch.chunk0[i] = segs[i].chunk0;
+            sch.kend[i] = (k += segs[i].n);
+        }
+        sch.first[g + 1] = i;
+        most = k > most ? k : most;
+    }
+    const uint32_t nblocks = 8u * div_up(most, kGroupXcds);
+#define ENERF_GS(CC, WW)                                                                                            \
+    do {                                                                                                            \
+        if (ev_start) { /* (the marker of launch_fwd) */                                                           \
+            hipExtLaunchKernelGGL(k_prof_mark, dim3(1), dim3(64), 0, s, nullptr, ev_start, 0);                      \
+            hipExtLaunchKernelGGL((k_grid_fwd_sweep<CC, WW>), dim3(nblocks), dim3(kPtsPerBlock), 0, s, nullptr,     \
+                                  ev_stop, 0, emb, offsets, outputs, B, L, tab, gridtype, layout, gen, sch);        \
+        } else                                                                                                      \
+            k_grid_fwd_sweep<CC, WW><<<nblocks, kPtsPerBlock, 0, s>>>(emb, offsets, outputs, B, L, tab, gridtype,  \
+                                                                      layout, gen, sch);                            \
+    } while (0)
+#define ENERF_GS_C(CC)                                                                                              \
+    do {                                                                                                            \
+        if (walk == 4) ENERF_GS(CC, 4);                                                                             \
+        else if (walk == 5) ENERF_GS(CC, 5);                                                                        \
+        else ENERF_GS(CC, 0);                                                                                       \
+    } while (0)
+    switch (C) {
+        case 1: ENERF_GS_C(1); break;
+        case 2: ENERF_GS_C(2); break;
+        case 4: ENERF_GS_C(4); break;
+        case 8: ENERF_GS_C(8); break;
+        default: ENERF_BADARG("GridEncoding: C must be 1, 2, 4, or 8.");
+    }
+#undef ENERF_GS_C
+#undef ENERF_GS
+    return 0;
+}
+
 // A deferred flush in progress: record lists written by one or more backward calls wait for k_grid_tile_adam.  The
 // list geometry (`region`) is fixed by the first call of the session.
 struct PendingRecords {
@@ -1748,6 +2073,30 @@ int enerf_debug_grid_level_mask(uint32_t mask) {
     return 0;
 }
 
+// testing / profiling aid: route of grid_encode_forward_sweep -- 0: the balanced schedule with a walker of `walk` levels
+// (0, 4 or 5; default 5), 1: the whole-level snake deal of k_grid_fwd, every level generating its own points
+int enerf_debug_sweep_route(uint32_t route, uint32_t walk) {
+    if (route > 1 || (walk != 0 && walk != 4 && walk != 5)) ENERF_BADARG("debug_sweep_route: route %u walk %u", route, walk);
+    g_sweep_route = route;
+    g_sweep_walk = walk;
+    return 0;
+}
+
+// testing aid: the sweep schedule of L levels, `nchunks` chunks each, as (pair, unit, first chunk, chunks) rows in
+// `out` (unit: a level, or 0x80000000 for the walker).  -> number of rows, or -1
+int enerf_debug_sweep_schedule(uint32_t L, uint32_t walk, uint32_t nchunks, uint32_t* out, uint32_t cap) {
+    if (L == 0 || L > kMaxLevels || nchunks == 0 || (walk != 0 && walk != 4 && walk != 5)) return -1;
+    SweepSeg segs[kMaxSweepSegs];
+    const int ns = build_sweep_schedule(L, walk, nchunks, segs, cap < kMaxSweepSegs ? cap : kMaxSweepSegs);
+    for (int i = 0; i < ns; i++) {
+        out[4 * i + 0] = segs[i].group;
+        out[4 * i + 1] = segs[i].unit;
+        out[4 * i + 2] = segs[i].chunk0;
+        out[4 * i + 3] = segs[i].n;
+    }
+    return ns;
+}
+
 // testing / profiling aid: fp32 batches of at least `min_batch` samples send the levels spanning at least `min_tiles`
 // 128-KiB tiles through the binned (record list + LDS tile) backward path; everything else takes the global-atomic
 // kernel.  Defaults 16384 / 8; min_batch 0xffffffff disables the binned path.
@@ -1806,8 +2155,12 @@ int enerf_grid_encode_forward_sweep(const void* embeddings, const int32_t* offse
     hipStream_t s = (hipStream_t)stream;
     ProfScope prof(ENERF_K_GRID_FWD, s, true);
     prof.units((double)B);
-    const int rc = launch_fwd<float, 3>(nullptr, (const float*)embeddings, offsets, (float*)outputs, B, C, L, tab, false,
-                                        (float*)nullptr, gridtype, out_layout, s, prof.start(), prof.stop(), gen);
+    const int rc = g_sweep_route == 1
+                       ? launch_fwd<float, 3>(nullptr, (const float*)embeddings, offsets, (float*)outputs, B, C, L, tab,
+                                              false, (float*)nullptr, gridtype, out_layout, s, prof.start(), prof.stop(),
+                                              gen)
+                       : launch_sweep((const float*)embeddings, offsets, (float*)outputs, B, C, L, tab, gridtype,
+                                      out_layout, gen, s, prof.start(), prof.stop());
     if (rc) return rc;
     ENERF_LAUNCH_CHECK("grid_encode_forward_sweep");
     return 0;

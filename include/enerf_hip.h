@@ -780,6 +780,13 @@ int enerf_train_step_events(const enerf_event_step_args* args);
 
 /* profiling aid: restrict grid_encode_forward/backward to the levels whose bit is set (default all) */
 int enerf_debug_grid_level_mask(uint32_t mask);
+/* Testing / profiling aid: route of grid_encode_forward_sweep.  0 (default): the static balanced schedule over the XCD
+ * pairs with the coarse levels 0 .. walk-1 taken by one thread per point (walk 0, 4 or 5; default 5); 1: the whole-level
+ * snake deal of the training forward. */
+int enerf_debug_sweep_route(uint32_t route, uint32_t walk);
+/* Testing aid: the sweep schedule of L levels of `nchunks` 256-point chunks as (XCD pair, unit, first chunk, chunks)
+ * rows, unit = level or 0x80000000 (the walker).  Returns the number of rows (at most `cap`), -1 on error. */
+int enerf_debug_sweep_schedule(uint32_t L, uint32_t walk, uint32_t nchunks, uint32_t* out, uint32_t cap);
 /* Testing / profiling aid: fp32 grid_encode_backward batches of at least `min_batch` samples send the levels spanning
  * at least `min_tiles` 128-KiB tiles through the binned path (per-tile record lists summed in LDS, no global float
  * atomics); everything else takes the global-atomic kernel.  Defaults 16384 / 8. */
