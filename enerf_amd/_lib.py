@@ -147,6 +147,10 @@ SIGNATURES = {
     "enerf_marching_cubes_workspace": [_u32, _c.POINTER(_c.c_uint64)],
     "enerf_marching_cubes_count": [_vp, _u32, _c.c_double, _vp, _vp, _vp],
     "enerf_marching_cubes_emit": [_vp, _u32, _c.c_double, _vp, _c.c_uint64, _c.c_uint64, _vp, _vp, _vp],
+    "enerf_eval_workspace": [_u32, _u32, _u32, _c.POINTER(_c.c_uint64)],
+    "enerf_eval_stats": [_vp, _vp, _u32, _u32, _u32, _int, _int, _vp, _vp, _vp],
+    "enerf_eval_correct": [_vp, _vp, _u32, _u32, _u32, _int, _vp, _vp, _vp, _vp, _vp, _vp],
+    "enerf_eval_ssim": [_vp, _vp, _u32, _u32, _u32, _u32, _c.c_double, _vp, _vp, _vp],
 }
 
 F32, F16, BF16 = 0, 1, 2

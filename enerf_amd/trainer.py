@@ -237,6 +237,15 @@ class TrainHarness:
         from .mesh import harness_save_mesh
         return harness_save_mesh(self, save_path, resolution, threshold)
 
+    def evaluate(self, views, opt, name="eval", save_dir=None, ema=None):
+        """The reference's Trainer.evaluate / evaluate_one_epoch (nerf/utils.py:763-766, 1028-1293) over `views` (the
+        val split's collate dicts): the renders of eval_step / eval_step_tumvie under model.eval() in this harness's
+        regime, PSNR and SSIM, or for `opt.event_only` the log-affine correction and its metrics; `ema` (store / copy_to /
+        restore) brackets the renders as there; rank 0 writes the validation/ tree under `save_dir`.  -> dict of floats
+        and lists (enerf_amd/evaluate.py)."""
+        from .evaluate import harness_evaluate
+        return harness_evaluate(self, views, opt, name=name, save_dir=save_dir, ema=ema)
+
     def load_checkpoint(self, checkpoint, model_only=False):
         """Resume from a checkpoint in the reference's format (nerf/utils.py:1353-1415), whoever wrote it."""
         from .checkpoint import load_checkpoint

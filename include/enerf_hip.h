@@ -55,8 +55,9 @@ const char* enerf_last_error(void);
  * 3: enerf_stratified_* added (the stratified sampler of NeRFRenderer.run).
  * 4: enerf_stratified_*_ex (fp16 storage of the colour rows / rgb / d rgb / dx) and enerf_mlp32_io16 (16-bit I/O of the
  *    enerf_mlp32_*_p calls) added: the stratified sampler's fp16 regime.
- * 5: enerf_mesh_lattice and enerf_marching_cubes_* added (mesh export, Trainer.save_mesh). */
-#define ENERF_ABI_VERSION 5
+ * 5: enerf_mesh_lattice and enerf_marching_cubes_* added (mesh export, Trainer.save_mesh).
+ * 6: enerf_eval_* added (held-out metrics, Trainer.evaluate_one_epoch). */
+#define ENERF_ABI_VERSION 6
 int enerf_abi_version(void);
 /* The library keeps grow-only scratch buffers per device (march chunk log, grid-backward record lists, ...).  Growing one
  * frees the old allocation; the counter returned here moves every time that happens.  A caller that captured library
@@ -905,6 +906,32 @@ int enerf_marching_cubes_count(const float* u, uint32_t R, double threshold, voi
                                enerf_stream_t stream);
 int enerf_marching_cubes_emit(const float* u, uint32_t R, double threshold, void* ws, uint64_t V, uint64_t F,
                               double* verts, int32_t* tris, enerf_stream_t stream);
+
+/* ------------------------------------------------------------------ evaluation metrics
+ * Trainer.evaluate_one_epoch (nerf/utils.py:44-92, 1028-1293), csrc/eval_metrics.hip; semantics in enerf_amd/evaluate.py
+ * and DESIGN.md 4.11.  V views of H x W pixels (H, W >= 7), C = 1 or 3 channels, fp32, stacked [V, H, W, C].  Every
+ * call writes its per-view results into res [V, ENERF_EVAL_COLS] fp64 (device), one column group per call, through
+ * per-workgroup partials in `ws` and a fixed-order second pass: no atomics, the same bits on every run.
+ *
+ * workspace: bytes of `ws` for V, H, W [host ptr]; one workspace serves the three calls in turn on one stream.
+ * stats: column 0 = sum over H*W*C of (pred - gt)^2 (the difference in fp32, squared and summed in fp64); log_mode != 0
+ *   adds columns 1..4 = the sums of x, y, x^2, xy with x = log(255 l(pred) + 1e-3), y = the same of gt in fp32, l = the
+ *   pixel (C = 1) or its esim luma (C = 3).
+ * correct (after stats with log_mode): ab [2] (device) = a, b of the least-squares fit of y on [1, x] over all V views
+ *   (fp64; a NaN becomes 5); pred_cor = exp(a x + b), gt_j = l(255 gt) as [V, H, W] fp32 planes; column 5 = the sum of
+ *   (gt_j - pred_cor)^2.
+ * ssim: column 6 = the mean over the (H - 6) x (W - 6) interior of skimage's SSIM map (7 x 7 uniform window, sample
+ *   covariance, K1 = 0.01, K2 = 0.03) of the planes x and y, read at pixel stride `stride` (1 .. 4) from [V, H, W, stride]. */
+#define ENERF_EVAL_COLS 7
+#define ENERF_EVAL_COL_SSE_COR 5
+#define ENERF_EVAL_COL_SSIM 6
+int enerf_eval_workspace(uint32_t V, uint32_t H, uint32_t W, uint64_t* bytes);
+int enerf_eval_stats(const float* pred, const float* gt, uint32_t V, uint32_t H, uint32_t W, int C, int log_mode,
+                     void* ws, double* res, enerf_stream_t stream);
+int enerf_eval_correct(const float* pred, const float* gt, uint32_t V, uint32_t H, uint32_t W, int C, void* ws,
+                       double* res, double* ab, float* pred_cor, float* gt_j, enerf_stream_t stream);
+int enerf_eval_ssim(const float* x, const float* y, uint32_t V, uint32_t H, uint32_t W, uint32_t stride,
+                    double data_range, void* ws, double* res, enerf_stream_t stream);
 
 #ifdef __cplusplus
 }
