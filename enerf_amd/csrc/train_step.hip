@@ -4,15 +4,20 @@
 //
 // Why: with the kernels of a 4096-ray step at ~0.32 ms, the ~28 launches of a step cost the Python harness ~0.4 ms of
 // host time (argument marshalling, tensor checks, dispatcher calls between the launches): the host, not the device,
-// bounds the step -- and under data parallelism it has the collectives to issue as well.  Here the host's share of a
-// step is one struct and one call; what remains on its side is the launches themselves.
+// bounds the step.  Here the host's share of a step is one struct and one call.
 //
-//   render of batch i (its samples were marched by the previous call, on the side stream):
-//     grid_encode_forward -> mlp32 forward (sigma net, + SH columns) -> mlp32 forward (colour net)
-//     -> composite forward + MSE + composite backward (one launch)
-//     -> mlp32 backward (colour net) -> mlp32 backward (sigma net; its reduce launch carries the signal the side stream
-//        waits for) -> [side stream: near_far + march_rays_train of batch i+1] -> grid_encode_backward (record lists)
-//     -> table Adam from the records + the MLP weights' Adam (one launch)
+// The step has three forms -- the RGB step (enerf_train_step_mse), the event step with both renders as one batch of 2 M
+// rows, the event step render by render -- and ONE body: a Batch of rows goes through
+//     forward():        grid_encode_forward (extra workgroups of its launch build the fused MLP's operand fragments)
+//                       -> nerf_mlp_forward, or mlp32 forward x 2 (sigma net + SH columns, colour net)
+//     [the form's own compositing forward, loss gradient, compositing backward]
+//     backward():       nerf_mlp_backward, or mlp32 backward x 2 (weight-gradient sums: a reduce launch, or the optimizer's)
+//     table_backward(): grid_encode_backward (record lists)
+//     optimizer():      table Adam from the records + the MLP weights' Adam (one launch)
+// The NEXT batch's march runs on the side stream behind the MLP backward, whose last launch carries the signal that stream
+// waits for (marches_side), or without a second stream: its count pass rides in the optimizer's launch, scan + write follow
+// it (marches_begin, optimizer).  Whatever a step arms in the other translation units is armed through its Step object,
+// which disarms on the way out.
 #include <hip/hip_runtime.h>
 
 #include <chrono>
@@ -41,366 +46,377 @@ extern "C" int enerf_debug_carry_count(int on) {
     return prev;
 }
 
+namespace {
+
+// The one-shots of a step: process-global requests in gridencoder.hip / mlp32.hip / raymarching.hip that the next matching
+// library call consumes.  One method arms each and remembers it; the destructor disarms what is still armed, so a step that
+// returns early leaves nothing behind for the next, unrelated call.
+class Step {
+public:
+    bool fused;                            // both nets as one launch each way (csrc/nerf_mlp.hip: the split-bf16 default)
+    PartialSums sums{nullptr, nullptr, 0, 0, 0};
+    MarchCountJob count_jobs[2] = {};      // the next marches riding in this step's optimizer launch (the first counts())
+
+    template <class A>
+    Step(const A* a, bool timed) : timed_(timed) {
+        if (a->mlp_precision >= 0) prev_prec_ = enerf_mlp32_precision(a->mlp_precision);
+        fused = a->nh_s == 1 && a->nh_c == 2 && enerf_nerf_mlp_available() != 0;
+        if (timed_) {
+            g_host_steps++;
+            t_prev_ = std::chrono::steady_clock::now();
+        }
+    }
+    Step(const Step&) = delete;
+    Step& operator=(const Step&) = delete;
+    ~Step() {
+        // (one-shot march requests never outlive the step they were armed for -- csrc/raymarching.hip: MarchOneShot)
+        enerf_march_fuse_near_far(nullptr, 0.0f);
+        enerf_march_mirror_count(nullptr);
+        grid_valid_rows(nullptr, 0, 0);
+        if (counts_) {                     // (failed between march_carry_begin and march_carry_end)
+            tile_adam_carry_count(nullptr);
+            march_carry_abort();
+        }
+        if (own_sums_) grid_adam_partial_sums(nullptr);
+        if (frags_) {                      // (the launch that should have carried the fragments' build never ran)
+            grid_fwd_carry(nullptr);
+            nerf_mlp_frags_invalidate();
+        }
+        if (defer_) enerf_mlp32_defer_reduce(0);
+        if (signal_) enerf_mlp32_signal_next_reduce(0);
+        if (mlp_rows_) enerf_mlp32_valid_rows(nullptr);
+        if (prev_prec_ >= 0) enerf_mlp32_precision(prev_prec_);
+    }
+
+    // Every timed call of the step passes its result through here: the host time since the previous one goes to the call's
+    // slot (enerf_debug_step_timing).  A call that stands for `slots` calls of the unfused route occupies as many; 0: the time
+    // is counted with the call that follows.
+    int run(int rc, int slots = 1) {
+        if (timed_) {
+            const auto t_now = std::chrono::steady_clock::now();
+            g_host_us[slot_ < 15 ? slot_ : 15] += std::chrono::duration<double, std::micro>(t_now - t_prev_).count();
+            t_prev_ = t_now;
+            slot_ += slots;
+        }
+        return rc;
+    }
+
+    void carry_frags(const SplitJob* job) {
+        grid_fwd_carry(job);
+        frags_ = true;
+    }
+    uint32_t frags_taken() {               // 1: the grid forward built the fragments, the MLP calls are told so
+        if (!frags_) return 0;
+        frags_ = false;
+        if (!grid_fwd_carry(nullptr)) return 1;
+        nerf_mlp_frags_invalidate();
+        return 0;
+    }
+    // (the budget's unfilled rows are skipped: real rows = base + min(*counter, cap), cap == 0: *counter; nullptr: all)
+    void grid_rows(const int32_t* counter, uint32_t base, uint32_t cap) { grid_valid_rows(counter, base, cap); }
+    void mlp_rows(const int32_t* counter, uint32_t base, uint32_t cap) {
+        if (!counter) return;
+        enerf_mlp32_valid_rows_ex(counter, base, cap);
+        mlp_rows_ = true;
+    }
+    void mlp_rows_off() {
+        if (mlp_rows_) enerf_mlp32_valid_rows(nullptr);
+        mlp_rows_ = false;
+    }
+    void defer_reduce(bool on) {
+        enerf_mlp32_defer_reduce(on ? 1 : 0);
+        defer_ = on;
+    }
+    void signal_next_reduce(bool on) {
+        enerf_mlp32_signal_next_reduce(on ? 1 : 0);
+        signal_ = on;
+    }
+    void own_sums(bool on) { own_sums_ = on; }       // `sums` is the job of the MLP backward that follows
+    bool has_sums() const { return own_sums_; }
+    void arm_sums() {
+        if (own_sums_) grid_adam_partial_sums(&sums);
+    }
+    bool sums_left() {                     // the optimizer's launch did not take them
+        const bool left = own_sums_ && grid_adam_partial_sums(nullptr);
+        own_sums_ = false;
+        return left;
+    }
+    uint32_t counts() const { return counts_; }
+    MarchCountJob* count_begin() { return &count_jobs[counts_]; }
+    void count_begun() { counts_++; }
+    void counts_drop() {                   // not this way after all: every march takes the side stream
+        march_carry_abort();
+        counts_ = 0;
+    }
+    void arm_counts() {
+        for (uint32_t q = 0; q < counts_; q++) tile_adam_carry_count(&count_jobs[q]);
+    }
+    bool counts_left() { return tile_adam_carry_count(nullptr); }
+    void counts_done() { counts_ = 0; }
+
+private:
+    int prev_prec_ = -1;
+    bool frags_ = false, mlp_rows_ = false, defer_ = false, signal_ = false, own_sums_ = false;
+    uint32_t counts_ = 0;
+    bool timed_;
+    int slot_ = 0;
+    std::chrono::steady_clock::time_point t_prev_;
+};
+
+// A batch of rows through the networks: the RGB step's M rows, the merged event step's 2 M, one render of the event step.
+struct Batch {
+    uint32_t rows, total;                  // total: the rows the record lists of the table backward reserve
+    const int32_t* counter;                // valid rows = base + min(*counter, cap) (cap == 0: *counter); nullptr: all
+    uint32_t base, cap;
+    const float *xyzs, *dirs;
+    float *feats, *h32, *fb_s, *fb_c, *sigma, *rgb, *g_sigmas, *g_rgbs, *dx32, *dfeat;
+    uint32_t overwrite;                    // weight gradients: 1 written, 0 added to what is there
+};
+template <class R>                         // (enerf_train_step_args and enerf_step_render name these fields alike)
+Batch batch_of(const R& r, uint32_t total, uint32_t overwrite) {
+    return {r.M,    total,  r.counter, 0,     0,          r.xyzs,   r.dirs, r.feats, r.h32,
+            r.fb_s, r.fb_c, r.sigma,   r.rgb, r.g_sigmas, r.g_rgbs, r.dx32, r.dfeat, overwrite};
+}
+
+struct NextMarch {
+    const float *rays_o, *rays_d;
+    uint32_t N, M;
+    float *nears, *fars, *xyzs, *dirs, *deltas;
+    int32_t *rays, *counter;
+};
+template <class R>
+uint32_t add_next(const R& r, NextMarch* list, uint32_t n) {
+    if (!r.next_rays_o) return n;
+    list[n] = {r.next_rays_o, r.next_rays_d, r.next_N,      r.next_M,    r.next_nears,  r.next_fars,
+               r.next_xyzs,   r.next_dirs,   r.next_deltas, r.next_rays, r.next_counter};
+    return n + 1;
+}
+
+// A: enerf_train_step_args or enerf_event_step_args (their network, march and optimizer fields carry the same names)
+
+// `carry`: the fused MLP's fragments may be built by the grid forward's launch (common.h SplitJob); `frags`: they are current
+template <class A>
+int forward(Step& st, const A* a, const Batch& b, bool carry, uint32_t frags) {
+    enerf_stream_t s = a->stream;
+    SplitJob job{};
+    if (st.fused && carry && g_carry_frags) {
+        if (int rc = st.run(nerf_mlp_frag_job(a->wseg_s, a->wseg_c, a->w0_cols_c, a->out_c, (hipStream_t)s, &job), 0)) return rc;
+        st.carry_frags(&job);
+    }
+    st.grid_rows(b.counter, b.base, b.cap);
+    if (int rc = st.run(enerf_grid_encode_forward(b.xyzs, a->embeddings, a->offsets, b.feats, b.rows, 3, 2, 16,
+                                                  a->level_scale_log2, a->base_resolution, 0, b.feats, a->gridtype, ENERF_F32,
+                                                  2, a->bound, a->inv_two_bound, s)))
+        return rc;
+    frags |= st.frags_taken();
+    st.mlp_rows(b.counter, b.base, b.cap);
+    int rc;
+    if (st.fused) {
+        rc = st.run(enerf_nerf_mlp_forward(b.feats, b.dirs, a->wseg_s, a->wseg_c, a->w0_cols_c, b.rows, a->out_c, b.sigma, b.rgb,
+                                           frags, s),
+                    2);
+    } else {
+        rc = st.run(enerf_mlp32_forward_p(b.feats, a->wseg_s, 32, 0, b.rows, 32, 16, a->nh_s, 0, 6, b.fb_s, b.h32, 1, 32, b.sigma,
+                                          b.dirs, s));
+        if (!rc)
+            rc = st.run(enerf_mlp32_forward_p(b.h32, a->wseg_c, a->w0_cols_c, 1, b.rows, 32, a->out_c, a->nh_c, 0, 3, b.fb_c, b.rgb,
+                                              0, 0, nullptr, nullptr, s));
+    }
+    st.mlp_rows_off();
+    return rc;
+}
+
+// `signal`: the last launch carries the signal the side stream's marches wait for; `fold`: the optimizer follows in this call
+// and may sum the fused backward's weight-gradient partial sums in its own launch (common.h PartialSums: no reduce launch)
+template <class A>
+int backward(Step& st, const A* a, const Batch& b, bool signal, bool fold) {
+    enerf_stream_t s = a->stream;
+    st.mlp_rows(b.counter, b.base, b.cap);
+    if (signal) st.signal_next_reduce(true);
+    int rc;
+    if (st.fused) {
+        if (fold && g_fold_reduce)
+            st.own_sums(nerf_mlp_partial_job(a->dwseg_s, a->dwseg_c, a->w0_cols_c, a->out_c, a->small_g, a->small_n, a->n_small,
+                                             b.rows, (hipStream_t)s, &st.sums) == 0);
+        rc = st.run(enerf_nerf_mlp_backward(b.g_rgbs, b.g_sigmas, 1.0f, b.feats, b.dirs, b.rgb, a->wseg_s, a->wseg_c, a->dwseg_s,
+                                            a->dwseg_c, a->w0_cols_c, b.overwrite, b.rows, a->out_c, b.dfeat,
+                                            st.has_sums() ? 3u : 1u, s),
+                    2);
+    } else {
+        st.defer_reduce(true);             // (the colour net's partial sums wait for the sigma net's reduce launch)
+        rc = st.run(enerf_mlp32_backward_p(b.g_rgbs, b.h32, a->wseg_c, a->dwseg_c, a->w0_cols_c, 1, b.overwrite, b.fb_c, b.rows,
+                                           32, a->out_c, a->nh_c, 0, nullptr, b.dx32, 0, 0, b.rgb, a->out_c, nullptr, nullptr, 0,
+                                           s));
+        if (!rc)
+            rc = st.run(enerf_mlp32_backward_p(b.dx32, b.feats, a->wseg_s, a->dwseg_s, 32, 0, b.overwrite, b.fb_s, b.rows, 32, 16,
+                                               a->nh_s, 0, nullptr, b.dfeat, 1, 32, nullptr, 0, b.g_sigmas, b.h32, 32, s));
+        st.defer_reduce(false);
+    }
+    st.mlp_rows_off();
+    if (signal) st.signal_next_reduce(false);
+    return rc;
+}
+
+// The next marches carried by the optimizer's launch where that applies: all of them or none (st.counts()).  Decided in front
+// of the MLP backward, because the side-stream form needs its signal armed there.
+template <class A>
+int marches_begin(Step& st, const A* a, const NextMarch* next, uint32_t n, bool carry) {
+    if (!carry || !g_carry_count || (a->march_flags & 16u)) return 0;
+    for (uint32_t q = 0; q < n; q++) {
+        const NextMarch& m = next[q];
+        enerf_march_fuse_near_far(a->aabb, a->min_near);           // (near / far inside the count pass)
+        const int b = march_carry_begin(m.rays_o, m.rays_d, a->bitfield, a->bound, a->dt_gamma, a->max_steps, m.N, a->cascade,
+                                        a->grid_size, m.M, m.nears, m.fars, m.xyzs, m.dirs, m.deltas, m.rays, m.counter,
+                                        a->perturb, a->march_flags, (hipStream_t)a->stream, st.count_begin(), n);
+        if (b < 0) return b;
+        if (b != 0) {
+            enerf_march_fuse_near_far(nullptr, 0.0f);              // (nothing consumed: the ordinary call arms it again)
+            st.counts_drop();
+            return 0;
+        }
+        st.count_begun();
+    }
+    return 0;
+}
+
+// ... and on the side stream, behind the MLP backward (a march reads no parameter)
+template <class A>
+int marches_side(Step& st, const A* a, const NextMarch* next, uint32_t n) {
+    enerf_stream_t ss = a->side_stream;
+    if (int rc = st.run(enerf_stream_wait_mlp32_signal(ss))) return rc;
+    for (uint32_t q = 0; q < n; q++) {
+        const NextMarch& m = next[q];
+        // (near / far inside the march's count pass: one launch less at the head of the chain the next step waits for)
+        if (int rc = st.run(enerf_march_fuse_near_far(a->aabb, a->min_near))) return rc;
+        if (int rc = st.run(enerf_march_rays_train_ex(m.rays_o, m.rays_d, a->bitfield, a->bound, a->dt_gamma, a->max_steps, m.N,
+                                                      a->cascade, a->grid_size, m.M, m.nears, m.fars, m.xyzs, m.dirs, m.deltas,
+                                                      m.rays, m.counter, a->perturb, a->march_flags, ss)))
+            return rc;
+    }
+    return 0;
+}
+
+// defer 1: record lists for the optimizer pass (b.total rows reserved); 0: the backward's own flush into the dense buffer
+template <class A>
+int table_backward(Step& st, const A* a, const Batch& b, uint32_t defer) {
+    st.grid_rows(b.counter, b.base, b.cap);
+    return st.run(enerf_grid_encode_backward_ex(b.dfeat, b.xyzs, a->embeddings, a->offsets, a->table_grad, b.rows, 3, 2, 16,
+                                                a->level_scale_log2, a->base_resolution, 0, b.dfeat, b.dfeat, a->gridtype,
+                                                ENERF_F32, 2, a->bound, a->inv_two_bound, defer, defer ? b.total : 0u,
+                                                a->stream));
+}
+
+// Table Adam from the records + the MLP weights' Adam, with what the step hands the launch (weight-gradient sums, count
+// passes), and the carried marches' scan + write behind it
+template <class A>
+int optimizer(Step& st, const A* a, const char* who) {
+    enerf_stream_t s = a->stream;
+    st.arm_sums();
+    st.arm_counts();
+    if (int rc = st.run(enerf_grid_adam_from_records_ex(a->table, a->table_grad, a->table_m, a->table_v, a->offsets, 16, 2, a->lr,
+                                                        a->beta1, a->beta2, a->eps, a->table_step, a->n_small, a->small_p,
+                                                        a->small_g, a->small_m, a->small_v, a->small_n, a->small_lr,
+                                                        a->small_step, s)))
+        return rc;
+    if (st.sums_left()) ENERF_BADARG("%s: the optimizer launch did not take the weight gradients' partial sums", who);
+    if (!st.counts()) return 0;
+    // (an optimizer form that carries nothing -- loss scaling armed -- leaves the jobs waiting: counted by launches of their own)
+    if (st.counts_left())
+        for (uint32_t q = 0; q < st.counts(); q++)
+            if (int rc = st.run(march_carry_count_now(&st.count_jobs[q], (hipStream_t)s))) return rc;
+    if (int rc = st.run(march_carry_end((hipStream_t)s))) return rc;
+    st.counts_done();
+    g_carried_steps++;
+    return 0;
+}
+
+// compositing of one render of the event step, on its sigma / rgb rows and their gradients
+int blend(const enerf_event_step_args* a, const enerf_step_render& r, const float* sigma, const float* rgb) {
+    return enerf_composite_rays_train_forward_blend(sigma, rgb, r.deltas, r.rays, r.M, r.N, r.weights_sum, nullptr, r.image,
+                                                    a->bg_color, 0, 0.0f, r.out_image, a->stream);
+}
+int blend_backward(const enerf_event_step_args* a, const enerf_step_render& r, const float* sigma, const float* rgb,
+                   float* g_sigmas, float* g_rgbs) {
+    // (its tail blocks zero the gradients of rows [counter, M): merged, the padding between the two renders' samples)
+    return enerf_composite_rays_train_backward_mse(r.g_image, nullptr, 1.0f, a->bg_color, 0, 0.0f, r.counter, sigma, rgb,
+                                                   r.deltas, r.rays, r.weights_sum, r.image, r.M, r.N, g_sigmas, g_rgbs, nullptr,
+                                                   a->stream);
+}
+// the event loss and its gradient with respect to the two images
+int event_loss(const enerf_event_step_args* a) {
+    return enerf_event_loss_fwd_bwd(a->r[0].out_image, a->r[1].out_image, a->pols, a->r[0].N, a->use_luma, a->linlog, a->C_thres,
+                                    a->log_thres, a->upstream, a->r[0].g_image, a->r[1].g_image, a->delta, a->loss, a->stream);
+}
+
+}  // namespace
+
 extern "C" int enerf_train_step_mse(const enerf_train_step_args* a) {
     if (!a) ENERF_BADARG("train_step_mse: null arguments");
     if (a->struct_bytes != sizeof(enerf_train_step_args))
         ENERF_BADARG("train_step_mse: struct of %u bytes, this library expects %zu", a->struct_bytes,
                      sizeof(enerf_train_step_args));
     if (a->M == 0 || a->N == 0) return 0;
-    enerf_stream_t s = a->stream;
-    const uint32_t M = a->M, N = a->N;
-    const float in_add = a->bound, in_mul = a->inv_two_bound;
-    int prev_prec = -1;
-    if (a->mlp_precision >= 0) prev_prec = enerf_mlp32_precision(a->mlp_precision);
-    int rc = 0;
-    bool rows_set = false, defer_set = false, signal_set = false, fused_mlp = false, carry_set = false, own_sums = false;
-    bool count_carried = false;
-    MarchCountJob count_job{};
-    uint32_t frags_built = 0;
-    PartialSums sums{nullptr, nullptr, 0, 0, 0};
-    int slot = 0;
-    auto t_prev = std::chrono::steady_clock::now();
-    if (g_host_timing) g_host_steps++;
-#define STEP(call)                                                                       \
-    do {                                                                                 \
-        rc = (call);                                                                     \
-        if (g_host_timing) {                                                             \
-            const auto t_now = std::chrono::steady_clock::now();                         \
-            g_host_us[slot < 15 ? slot : 15] += std::chrono::duration<double, std::micro>(t_now - t_prev).count(); \
-            t_prev = t_now;                                                              \
-            slot++;                                                                      \
-        }                                                                                \
-        if (rc) goto done;                                                               \
-    } while (0)
-    // ---- forward
-    // (both nets as one launch each way when the arithmetic is the split-bf16 default: csrc/nerf_mlp.hip; their operand
-    //  fragments are then built by sixteen extra workgroups of the grid forward's launch -- common.h SplitJob)
-    fused_mlp = a->nh_s == 1 && a->nh_c == 2 && enerf_nerf_mlp_available() != 0;
-    if (fused_mlp && g_carry_frags) {
-        SplitJob job;
-        STEP(nerf_mlp_frag_job(a->wseg_s, a->wseg_c, a->w0_cols_c, a->out_c, (hipStream_t)s, &job));
-        if (g_host_timing) slot--;
-        grid_fwd_carry(&job);
-        carry_set = true;
-    }
-    if (a->counter) grid_valid_rows(a->counter, 0, 0);      // (forward .. backward: the budget's unfilled rows are skipped)
-    STEP(enerf_grid_encode_forward(a->xyzs, a->embeddings, a->offsets, a->feats, M, 3, 2, 16, a->level_scale_log2,
-                                   a->base_resolution, 0, a->feats, a->gridtype, ENERF_F32, 2, in_add, in_mul, s));
-    if (carry_set) {
-        frags_built = grid_fwd_carry(nullptr) ? 0u : 1u;      // (taken along: the MLP calls are told so)
-        if (!frags_built) nerf_mlp_frags_invalidate();
-        carry_set = false;
-    }
-    if (a->counter) {
-        enerf_mlp32_valid_rows(a->counter);
-        rows_set = true;
-    }
-    if (fused_mlp) {
-        STEP(enerf_nerf_mlp_forward(a->feats, a->dirs, a->wseg_s, a->wseg_c, a->w0_cols_c, M, a->out_c, a->sigma, a->rgb,
-                                    frags_built, s));
-        if (g_host_timing) slot++;
-    } else {
-        STEP(enerf_mlp32_forward_p(a->feats, a->wseg_s, 32, 0, M, 32, 16, a->nh_s, 0, 6, a->fb_s, a->h32, 1, 32, a->sigma,
-                                   a->dirs, s));
-        STEP(enerf_mlp32_forward_p(a->h32, a->wseg_c, a->w0_cols_c, 1, M, 32, a->out_c, a->nh_c, 0, 3, a->fb_c, a->rgb, 0, 0,
-                                   nullptr, nullptr, s));
-    }
-    // ---- compositing forward + loss gradient + compositing backward
-    STEP(enerf_composite_rays_train_fwd_bwd_mse(a->sigma, a->rgb, a->deltas, a->rays, M, N, a->weights_sum, a->image,
-                                                nullptr, 0, a->bg_scalar, a->out_image, a->target, a->grad_scale,
-                                                a->counter, a->g_sigmas, a->g_rgbs, a->loss, s));
-    // ---- the next batch's march: carried by the optimizer's launch where that applies (decided here, because the
-    //      side-stream form needs its signal armed on the MLP backward)
-    if (a->next_rays_o && g_carry_count && !(a->flags & 1u) && !(a->march_flags & 16u)) {
-        enerf_march_fuse_near_far(a->aabb, a->min_near);           // (near / far inside the count pass)
-        const int b = march_carry_begin(a->next_rays_o, a->next_rays_d, a->bitfield, a->bound, a->dt_gamma, a->max_steps,
-                                        a->next_N, a->cascade, a->grid_size, a->next_M, a->next_nears, a->next_fars,
-                                        a->next_xyzs, a->next_dirs, a->next_deltas, a->next_rays, a->next_counter,
-                                        a->perturb, a->march_flags, (hipStream_t)s, &count_job);
-        if (b < 0) { rc = b; goto done; }
-        count_carried = b == 0;
-        if (!count_carried) enerf_march_fuse_near_far(nullptr, 0.0f);    // (nothing consumed: the ordinary call arms it again)
-    }
-    // ---- MLP backward (the colour net's partial sums wait for the sigma net's reduce launch)
-    if (a->next_rays_o && !count_carried) {
-        enerf_mlp32_signal_next_reduce(1);
-        signal_set = true;
-    }
-    if (fused_mlp) {
-        // (the weight gradients' partial sums are summed by the optimizer's launch when it follows in this call and its small
-        //  tensors are those gradients: no reduce launch in between -- common.h PartialSums)
-        if (g_fold_reduce && !(a->flags & 1u))
-            own_sums = nerf_mlp_partial_job(a->dwseg_s, a->dwseg_c, a->w0_cols_c, a->out_c, a->small_g, a->small_n, a->n_small,
-                                            M, (hipStream_t)s, &sums) == 0;
-        STEP(enerf_nerf_mlp_backward(a->g_rgbs, a->g_sigmas, 1.0f, a->feats, a->dirs, a->rgb, a->wseg_s, a->wseg_c,
-                                     a->dwseg_s, a->dwseg_c, a->w0_cols_c, 1, M, a->out_c, a->dfeat, own_sums ? 3u : 1u, s));
-        if (g_host_timing) slot++;
-    } else {
-        enerf_mlp32_defer_reduce(1);
-        defer_set = true;
-        STEP(enerf_mlp32_backward_p(a->g_rgbs, a->h32, a->wseg_c, a->dwseg_c, a->w0_cols_c, 1, 1, a->fb_c, M, 32, a->out_c,
-                                    a->nh_c, 0, nullptr, a->dx32, 0, 0, a->rgb, a->out_c, nullptr, nullptr, 0, s));
-        STEP(enerf_mlp32_backward_p(a->dx32, a->feats, a->wseg_s, a->dwseg_s, 32, 0, 1, a->fb_s, M, 32, 16, a->nh_s, 0,
-                                    nullptr, a->dfeat, 1, 32, nullptr, 0, a->g_sigmas, a->h32, 32, s));
-        enerf_mlp32_defer_reduce(0);
-        defer_set = false;
-    }
-    if (rows_set) {
-        enerf_mlp32_valid_rows(nullptr);
-        rows_set = false;
-    }
-    // ---- the next batch's march, on the side stream, behind the MLP backward (it reads no parameter)
-    if (a->next_rays_o && !count_carried) {
-        enerf_mlp32_signal_next_reduce(0);
-        signal_set = false;
-        enerf_stream_t ss = a->side_stream;
-        STEP(enerf_stream_wait_mlp32_signal(ss));
-        // (near / far of the next batch inside the count pass: one launch less at the head of the chain the next step waits for)
-        STEP(enerf_march_fuse_near_far(a->aabb, a->min_near));
-        STEP(enerf_march_rays_train_ex(a->next_rays_o, a->next_rays_d, a->bitfield, a->bound, a->dt_gamma, a->max_steps,
-                                       a->next_N, a->cascade, a->grid_size, a->next_M, a->next_nears, a->next_fars,
-                                       a->next_xyzs, a->next_dirs, a->next_deltas, a->next_rays, a->next_counter, a->perturb,
-                                       a->march_flags, ss));
-    }
-    // ---- table backward (record lists) and the optimizer
-    if (a->flags & 1u) {
-        // data parallel: the gradient has to exist to be averaged -- the backward's own flush into the dense buffer
-        // (flags bit 1: the sharded tail with an owner range set -- enerf_grid_owner_range -- keeps this rank's own
-        //  slice as record lists for the optimizer pass and flushes the rest)
-        STEP(enerf_grid_encode_backward_ex(a->dfeat, a->xyzs, a->embeddings, a->offsets, a->table_grad, M, 3, 2, 16,
-                                           a->level_scale_log2, a->base_resolution, 0, a->dfeat, a->dfeat, a->gridtype,
-                                           ENERF_F32, 2, in_add, in_mul, (a->flags & 2u) ? 1u : 0u, (a->flags & 2u) ? M : 0u,
-                                           s));
-        goto done;
-    }
-    STEP(enerf_grid_encode_backward_ex(a->dfeat, a->xyzs, a->embeddings, a->offsets, a->table_grad, M, 3, 2, 16,
-                                       a->level_scale_log2, a->base_resolution, 0, a->dfeat, a->dfeat, a->gridtype,
-                                       ENERF_F32, 2, in_add, in_mul, 1, M, s));
-    if (own_sums) grid_adam_partial_sums(&sums);
-    if (count_carried) tile_adam_carry_count(&count_job);
-    STEP(enerf_grid_adam_from_records_ex(a->table, a->table_grad, a->table_m, a->table_v, a->offsets, 16, 2, a->lr,
-                                         a->beta1, a->beta2, a->eps, a->table_step, a->n_small, a->small_p, a->small_g,
-                                         a->small_m, a->small_v, a->small_n, a->small_lr, a->small_step, s));
-    if (own_sums && grid_adam_partial_sums(nullptr)) {
-        set_error("train_step_mse: the optimizer launch did not take the weight gradients' partial sums");
-        rc = ENERF_E_BADARG;
-    }
-    own_sums = false;
-    if (count_carried && !rc) {
-        // (an optimizer form that carries nothing -- loss scaling armed -- leaves the job waiting: counted by its own launch)
-        if (tile_adam_carry_count(nullptr)) STEP(march_carry_count_now(&count_job, (hipStream_t)s));
-        STEP(march_carry_end((hipStream_t)s));
-        count_carried = false;
-        g_carried_steps++;
-    }
-done:
-#undef STEP
-    // (one-shot march requests never outlive the step they were armed for -- csrc/raymarching.hip: MarchOneShot)
-    enerf_march_fuse_near_far(nullptr, 0.0f);
-    enerf_march_mirror_count(nullptr);
-    grid_valid_rows(nullptr, 0, 0);
-    if (count_carried) {                   // (failed between march_carry_begin and march_carry_end)
-        tile_adam_carry_count(nullptr);
-        march_carry_abort();
-    }
-    if (own_sums) grid_adam_partial_sums(nullptr);
-    if (carry_set) {                       // (the launch that should have carried the fragments' build never ran)
-        grid_fwd_carry(nullptr);
-        nerf_mlp_frags_invalidate();
-    }
-    if (defer_set) enerf_mlp32_defer_reduce(0);
-    if (signal_set) enerf_mlp32_signal_next_reduce(0);
-    if (rows_set) enerf_mlp32_valid_rows(nullptr);
-    if (prev_prec >= 0) enerf_mlp32_precision(prev_prec);
-    return rc;
+    Step st(a, g_host_timing);
+    // flags bit 0, data parallel: the gradient has to exist to be averaged -- no optimizer here, so nothing rides in its launch
+    const bool dp = (a->flags & 1u) != 0;
+    const Batch b = batch_of(*a, a->M, 1);
+    NextMarch next[1];
+    const uint32_t n_next = add_next(*a, next, 0);
+    if (int rc = forward(st, a, b, true, 0)) return rc;
+    // compositing forward + loss gradient + compositing backward
+    if (int rc = st.run(enerf_composite_rays_train_fwd_bwd_mse(a->sigma, a->rgb, a->deltas, a->rays, a->M, a->N, a->weights_sum,
+                                                               a->image, nullptr, 0, a->bg_scalar, a->out_image, a->target,
+                                                               a->grad_scale, a->counter, a->g_sigmas, a->g_rgbs, a->loss,
+                                                               a->stream)))
+        return rc;
+    if (int rc = marches_begin(st, a, next, n_next, !dp)) return rc;
+    const bool side = n_next && !st.counts();
+    if (int rc = backward(st, a, b, side, !dp)) return rc;
+    if (side)
+        if (int rc = marches_side(st, a, next, n_next)) return rc;
+    // (flags bit 1: the sharded tail with an owner range set -- enerf_grid_owner_range -- keeps this rank's own slice as
+    //  record lists for the optimizer pass and flushes the rest)
+    if (dp) return table_backward(st, a, b, (a->flags & 2u) ? 1u : 0u);
+    if (int rc = table_backward(st, a, b, 1)) return rc;
+    return optimizer(st, a, "train_step_mse");
 }
 
-// The event-only step with both renders' samples as ONE batch of 2 M rows (enerf_event_step_args.flags bit 1)
+// The event-only step with both renders' samples as ONE batch of 2 M rows (enerf_event_step_args.flags bit 1): compositing
+// stays per render, on the halves.  Real rows: the first render's M + min(counter_2, M).
 static int train_step_events_merged(const enerf_event_step_args* a) {
-    enerf_stream_t s = a->stream;
     const enerf_step_render &r0 = a->r[0], &r1 = a->r[1];
-    const uint32_t N = r0.N, M = r0.M, M2 = 2 * M;
-    const float in_add = a->bound, in_mul = a->inv_two_bound;
+    const uint32_t M = r0.M, M2 = 2 * M;
     if (r1.M != M || r1.xyzs != r0.xyzs + (size_t)3 * M || r1.dirs != r0.dirs + (size_t)3 * M ||
         r1.deltas != r0.deltas + (size_t)2 * M)
         ENERF_BADARG("train_step_events(merged): the second render's samples must follow the first's M rows");
     if (!a->m_feats || !a->m_h32 || !a->m_sigma || !a->m_rgb || !a->m_g_sigmas || !a->m_g_rgbs || !a->m_dx32 || !a->m_dfeat)
         ENERF_BADARG("train_step_events(merged): the m_* scratch buffers are required");
-    int prev_prec = -1;
-    if (a->mlp_precision >= 0) prev_prec = enerf_mlp32_precision(a->mlp_precision);
-    int rc = 0;
-    bool rows_set = false, defer_set = false, signal_set = false, carry_set = false, own_sums = false;
-    uint32_t counts_carried = 0;           // the next step's marches riding in this step's optimizer launch
-    MarchCountJob count_jobs[2] = {};
-    uint32_t frags_built = 0;
-    PartialSums sums{nullptr, nullptr, 0, 0, 0};
-    const bool march_next = r0.next_rays_o != nullptr || r1.next_rays_o != nullptr;
+    Step st(a, false);
     const bool skip = r0.counter != nullptr && r1.counter != nullptr;
-    const bool fused_mlp = a->nh_s == 1 && a->nh_c == 2 && enerf_nerf_mlp_available() != 0;
-#define STEP(call)           \
-    do {                     \
-        rc = (call);         \
-        if (rc) goto done;   \
-    } while (0)
-    // (as in enerf_train_step_mse: the operand fragments' build rides in the grid forward's launch, the weight gradients'
-    //  partial sums are summed by the optimizer's launch)
-    if (fused_mlp && g_carry_frags) {
-        SplitJob job;
-        STEP(nerf_mlp_frag_job(a->wseg_s, a->wseg_c, a->w0_cols_c, a->out_c, (hipStream_t)s, &job));
-        grid_fwd_carry(&job);
-        carry_set = true;
-    }
-    if (skip) grid_valid_rows(r1.counter, M, M);            // (real rows: the first render's M + min(counter_2, M))
-    STEP(enerf_grid_encode_forward(r0.xyzs, a->embeddings, a->offsets, a->m_feats, M2, 3, 2, 16, a->level_scale_log2,
-                                   a->base_resolution, 0, a->m_feats, a->gridtype, ENERF_F32, 2, in_add, in_mul, s));
-    if (carry_set) {
-        frags_built = grid_fwd_carry(nullptr) ? 0u : 1u;
-        if (!frags_built) nerf_mlp_frags_invalidate();
-        carry_set = false;
-    }
-    if (skip) {
-        enerf_mlp32_valid_rows_ex(r1.counter, M, M);         // real rows: the first render's M + min(counter_2, M)
-        rows_set = true;
-    }
-    if (fused_mlp) {
-        STEP(enerf_nerf_mlp_forward(a->m_feats, r0.dirs, a->wseg_s, a->wseg_c, a->w0_cols_c, M2, a->out_c, a->m_sigma,
-                                    a->m_rgb, frags_built, s));
-    } else {
-        STEP(enerf_mlp32_forward_p(a->m_feats, a->wseg_s, 32, 0, M2, 32, 16, a->nh_s, 0, 6, a->m_fb_s, a->m_h32, 1, 32,
-                                   a->m_sigma, r0.dirs, s));
-        STEP(enerf_mlp32_forward_p(a->m_h32, a->wseg_c, a->w0_cols_c, 1, M2, 32, a->out_c, a->nh_c, 0, 3, a->m_fb_c, a->m_rgb,
-                                   0, 0, nullptr, nullptr, s));
-    }
-    if (rows_set) {
-        enerf_mlp32_valid_rows(nullptr);
-        rows_set = false;
-    }
-    for (int k = 0; k < 2; k++) {
-        const enerf_step_render& r = a->r[k];
-        STEP(enerf_composite_rays_train_forward_blend(a->m_sigma + (size_t)k * M, a->m_rgb + (size_t)k * M * a->out_c, r.deltas,
-                                                      r.rays, M, N, r.weights_sum, nullptr, r.image, a->bg_color, 0, 0.0f,
-                                                      r.out_image, s));
-    }
-    STEP(enerf_event_loss_fwd_bwd(r0.out_image, r1.out_image, a->pols, N, a->use_luma, a->linlog, a->C_thres, a->log_thres,
-                                  a->upstream, r0.g_image, r1.g_image, a->delta, a->loss, s));
-    for (int k = 0; k < 2; k++) {
-        const enerf_step_render& r = a->r[k];
-        // (its tail blocks zero the gradients of rows [counter, M): the padding between the two renders' samples)
-        STEP(enerf_composite_rays_train_backward_mse(r.g_image, nullptr, 1.0f, a->bg_color, 0, 0.0f, r.counter,
-                                                     a->m_sigma + (size_t)k * M, a->m_rgb + (size_t)k * M * a->out_c, r.deltas,
-                                                     r.rays, r.weights_sum, r.image, M, N, a->m_g_sigmas + (size_t)k * M,
-                                                     a->m_g_rgbs + (size_t)k * M * a->out_c, nullptr, s));
-    }
-    if (skip) {
-        enerf_mlp32_valid_rows_ex(r1.counter, M, M);
-        rows_set = true;
-    }
-    // ---- the next step's two marches: carried by the optimizer's launch where that applies (both or neither; decided here,
-    //      because the side-stream form needs its signal armed on the MLP backward)
-    if (march_next && g_carry_count && !(a->march_flags & 16u)) {
-        const uint32_t want = (r0.next_rays_o ? 1u : 0u) + (r1.next_rays_o ? 1u : 0u);
-        for (int q = 0; q < 2; q++) {
-            const enerf_step_render& n = a->r[q];
-            if (!n.next_rays_o) continue;
-            enerf_march_fuse_near_far(a->aabb, a->min_near);       // (near / far inside the count pass)
-            const int b = march_carry_begin(n.next_rays_o, n.next_rays_d, a->bitfield, a->bound, a->dt_gamma, a->max_steps,
-                                            n.next_N, a->cascade, a->grid_size, n.next_M, n.next_nears, n.next_fars,
-                                            n.next_xyzs, n.next_dirs, n.next_deltas, n.next_rays, n.next_counter, a->perturb,
-                                            a->march_flags, (hipStream_t)s, &count_jobs[counts_carried], want);
-            if (b < 0) { rc = b; goto done; }
-            if (b != 0) {                                           // not this way: both marches take the side stream
-                enerf_march_fuse_near_far(nullptr, 0.0f);
-                march_carry_abort();
-                counts_carried = 0;
-                break;
-            }
-            counts_carried++;
-        }
-    }
-    if (march_next && !counts_carried) {
-        enerf_mlp32_signal_next_reduce(1);
-        signal_set = true;
-    }
-    if (fused_mlp) {
-        if (g_fold_reduce)
-            own_sums = nerf_mlp_partial_job(a->dwseg_s, a->dwseg_c, a->w0_cols_c, a->out_c, a->small_g, a->small_n, a->n_small,
-                                            M2, (hipStream_t)s, &sums) == 0;
-        STEP(enerf_nerf_mlp_backward(a->m_g_rgbs, a->m_g_sigmas, 1.0f, a->m_feats, r0.dirs, a->m_rgb, a->wseg_s, a->wseg_c,
-                                     a->dwseg_s, a->dwseg_c, a->w0_cols_c, 1u, M2, a->out_c, a->m_dfeat, own_sums ? 3u : 1u, s));
-    } else {
-        enerf_mlp32_defer_reduce(1);
-        defer_set = true;
-        STEP(enerf_mlp32_backward_p(a->m_g_rgbs, a->m_h32, a->wseg_c, a->dwseg_c, a->w0_cols_c, 1, 1u, a->m_fb_c, M2, 32,
-                                    a->out_c, a->nh_c, 0, nullptr, a->m_dx32, 0, 0, a->m_rgb, a->out_c, nullptr, nullptr, 0, s));
-        STEP(enerf_mlp32_backward_p(a->m_dx32, a->m_feats, a->wseg_s, a->dwseg_s, 32, 0, 1u, a->m_fb_s, M2, 32, 16, a->nh_s, 0,
-                                    nullptr, a->m_dfeat, 1, 32, nullptr, 0, a->m_g_sigmas, a->m_h32, 32, s));
-        enerf_mlp32_defer_reduce(0);
-        defer_set = false;
-    }
-    if (rows_set) {
-        enerf_mlp32_valid_rows(nullptr);
-        rows_set = false;
-    }
-    if (march_next && !counts_carried) {
-        enerf_mlp32_signal_next_reduce(0);
-        signal_set = false;
-        enerf_stream_t ss = a->side_stream;
-        STEP(enerf_stream_wait_mlp32_signal(ss));
-        for (int q = 0; q < 2; q++) {
-            const enerf_step_render& n = a->r[q];
-            if (!n.next_rays_o) continue;
-            STEP(enerf_march_fuse_near_far(a->aabb, a->min_near));       // (near / far inside the march's count pass)
-            STEP(enerf_march_rays_train_ex(n.next_rays_o, n.next_rays_d, a->bitfield, a->bound, a->dt_gamma, a->max_steps,
-                                           n.next_N, a->cascade, a->grid_size, n.next_M, n.next_nears, n.next_fars,
-                                           n.next_xyzs, n.next_dirs, n.next_deltas, n.next_rays, n.next_counter, a->perturb,
-                                           a->march_flags, ss));
-        }
-    }
-    STEP(enerf_grid_encode_backward_ex(a->m_dfeat, r0.xyzs, a->embeddings, a->offsets, a->table_grad, M2, 3, 2, 16,
-                                       a->level_scale_log2, a->base_resolution, 0, a->m_dfeat, a->m_dfeat, a->gridtype,
-                                       ENERF_F32, 2, in_add, in_mul, 1, M2, s));
-    if (own_sums) grid_adam_partial_sums(&sums);
-    for (uint32_t q = 0; q < counts_carried; q++) tile_adam_carry_count(&count_jobs[q]);
-    STEP(enerf_grid_adam_from_records_ex(a->table, a->table_grad, a->table_m, a->table_v, a->offsets, 16, 2, a->lr, a->beta1,
-                                         a->beta2, a->eps, a->table_step, a->n_small, a->small_p, a->small_g, a->small_m,
-                                         a->small_v, a->small_n, a->small_lr, a->small_step, s));
-    if (own_sums && grid_adam_partial_sums(nullptr)) {
-        set_error("train_step_events: the optimizer launch did not take the weight gradients' partial sums");
-        rc = ENERF_E_BADARG;
-    }
-    own_sums = false;
-    if (counts_carried && !rc) {
-        // (an optimizer form that carries nothing leaves the jobs waiting: counted by launches of their own)
-        if (tile_adam_carry_count(nullptr))
-            for (uint32_t q = 0; q < counts_carried; q++) STEP(march_carry_count_now(&count_jobs[q], (hipStream_t)s));
-        STEP(march_carry_end((hipStream_t)s));
-        counts_carried = 0;
-        g_carried_steps++;
-    }
-done:
-#undef STEP
-    // (one-shot march requests never outlive the step they were armed for -- csrc/raymarching.hip: MarchOneShot)
-    enerf_march_fuse_near_far(nullptr, 0.0f);
-    enerf_march_mirror_count(nullptr);
-    grid_valid_rows(nullptr, 0, 0);
-    if (counts_carried) {                  // (failed between march_carry_begin and march_carry_end)
-        tile_adam_carry_count(nullptr);
-        march_carry_abort();
-    }
-    if (own_sums) grid_adam_partial_sums(nullptr);
-    if (carry_set) {                       // (the launch that should have carried the fragments' build never ran)
-        grid_fwd_carry(nullptr);
-        nerf_mlp_frags_invalidate();
-    }
-    if (defer_set) enerf_mlp32_defer_reduce(0);
-    if (signal_set) enerf_mlp32_signal_next_reduce(0);
-    if (rows_set) enerf_mlp32_valid_rows(nullptr);
-    if (prev_prec >= 0) enerf_mlp32_precision(prev_prec);
-    return rc;
+    const Batch b = {M2,         M2,      skip ? r1.counter : nullptr, M, M, r0.xyzs, r0.dirs, a->m_feats, a->m_h32, a->m_fb_s,
+                     a->m_fb_c,  a->m_sigma, a->m_rgb, a->m_g_sigmas, a->m_g_rgbs, a->m_dx32, a->m_dfeat, 1};
+    NextMarch next[2];
+    const uint32_t n_next = add_next(r1, next, add_next(r0, next, 0));
+    if (int rc = forward(st, a, b, true, 0)) return rc;
+    for (size_t k = 0; k < 2; k++)
+        if (int rc = blend(a, a->r[k], b.sigma + k * M, b.rgb + k * M * a->out_c)) return rc;
+    if (int rc = event_loss(a)) return rc;
+    for (size_t k = 0; k < 2; k++)
+        if (int rc = blend_backward(a, a->r[k], b.sigma + k * M, b.rgb + k * M * a->out_c, b.g_sigmas + k * M,
+                                    b.g_rgbs + k * M * a->out_c))
+            return rc;
+    if (int rc = marches_begin(st, a, next, n_next, true)) return rc;
+    const bool side = n_next && !st.counts();
+    if (int rc = backward(st, a, b, side, true)) return rc;
+    if (side)
+        if (int rc = marches_side(st, a, next, n_next)) return rc;
+    if (int rc = table_backward(st, a, b, 1)) return rc;
+    return optimizer(st, a, "train_step_events");
 }
 
 // The event-only step (two renders, one loss, one optimizer pass): events.train_step_events_manual +
-// FusedAdam.step_grid_table, call for call.
+// FusedAdam.step_grid_table, call for call.  Render by render, nothing rides in another launch: no fragments, weight-gradient
+// sums or marches are carried; the second render finds the first's fragments and adds its weight gradients to the first's.
 extern "C" int enerf_train_step_events(const enerf_event_step_args* a) {
     if (!a) ENERF_BADARG("train_step_events: null arguments");
     if (a->struct_bytes != sizeof(enerf_event_step_args))
@@ -410,116 +426,26 @@ extern "C" int enerf_train_step_events(const enerf_event_step_args* a) {
         ENERF_BADARG("train_step_events: both renders take the same (non-zero) number of rays and a sample budget");
     if (!a->bg_color || !a->pols) ENERF_BADARG("train_step_events: bg_color and pols are required");
     if (a->flags & 2u) return train_step_events_merged(a);
-    enerf_stream_t s = a->stream;
-    const uint32_t N = a->r[0].N, total = a->r[0].M + a->r[1].M;
-    const float in_add = a->bound, in_mul = a->inv_two_bound;
-    int prev_prec = -1;
-    if (a->mlp_precision >= 0) prev_prec = enerf_mlp32_precision(a->mlp_precision);
-    int rc = 0;
-    bool rows_set = false, defer_set = false, signal_set = false;
-    const bool march_next = a->r[0].next_rays_o != nullptr || a->r[1].next_rays_o != nullptr;
-    const bool fused_mlp = a->nh_s == 1 && a->nh_c == 2 && enerf_nerf_mlp_available() != 0;
-#define STEP(call)           \
-    do {                     \
-        rc = (call);         \
-        if (rc) goto done;   \
-    } while (0)
-    // ---- the two renders' forward
-    for (int k = 0; k < 2; k++) {
-        const enerf_step_render& r = a->r[k];
-        grid_valid_rows(r.counter, 0, 0);
-        STEP(enerf_grid_encode_forward(r.xyzs, a->embeddings, a->offsets, r.feats, r.M, 3, 2, 16, a->level_scale_log2,
-                                       a->base_resolution, 0, r.feats, a->gridtype, ENERF_F32, 2, in_add, in_mul, s));
-        if (r.counter) {
-            enerf_mlp32_valid_rows(r.counter);
-            rows_set = true;
-        }
-        if (fused_mlp) {
-            STEP(enerf_nerf_mlp_forward(r.feats, r.dirs, a->wseg_s, a->wseg_c, a->w0_cols_c, r.M, a->out_c, r.sigma, r.rgb,
-                                        k == 0 ? 0u : 1u, s));
-        } else {
-            STEP(enerf_mlp32_forward_p(r.feats, a->wseg_s, 32, 0, r.M, 32, 16, a->nh_s, 0, 6, r.fb_s, r.h32, 1, 32, r.sigma,
-                                       r.dirs, s));
-            STEP(enerf_mlp32_forward_p(r.h32, a->wseg_c, a->w0_cols_c, 1, r.M, 32, a->out_c, a->nh_c, 0, 3, r.fb_c, r.rgb, 0,
-                                       0, nullptr, nullptr, s));
-        }
-        if (rows_set) {
-            enerf_mlp32_valid_rows(nullptr);
-            rows_set = false;
-        }
-        STEP(enerf_composite_rays_train_forward_blend(r.sigma, r.rgb, r.deltas, r.rays, r.M, N, r.weights_sum, nullptr,
-                                                      r.image, a->bg_color, 0, 0.0f, r.out_image, s));
+    Step st(a, false);
+    const uint32_t total = a->r[0].M + a->r[1].M;
+    const Batch b[2] = {batch_of(a->r[0], total, 1), batch_of(a->r[1], total, 0)};
+    NextMarch next[2];
+    const uint32_t n_next = add_next(a->r[1], next, add_next(a->r[0], next, 0));
+    for (uint32_t k = 0; k < 2; k++) {
+        if (int rc = forward(st, a, b[k], false, k)) return rc;
+        if (int rc = blend(a, a->r[k], b[k].sigma, b[k].rgb)) return rc;
     }
-    // ---- the loss and its gradient with respect to the two images
-    STEP(enerf_event_loss_fwd_bwd(a->r[0].out_image, a->r[1].out_image, a->pols, N, a->use_luma, a->linlog, a->C_thres,
-                                  a->log_thres, a->upstream, a->r[0].g_image, a->r[1].g_image, a->delta, a->loss, s));
-    // ---- the two renders' backward (the second adds its weight gradients to the first's)
-    for (int k = 0; k < 2; k++) {
-        const enerf_step_render& r = a->r[k];
-        STEP(enerf_composite_rays_train_backward_mse(r.g_image, nullptr, 1.0f, a->bg_color, 0, 0.0f, r.counter, r.sigma,
-                                                     r.rgb, r.deltas, r.rays, r.weights_sum, r.image, r.M, N, r.g_sigmas,
-                                                     r.g_rgbs, nullptr, s));
-        if (r.counter) {
-            enerf_mlp32_valid_rows(r.counter);
-            rows_set = true;
-        }
-        if (k == 1 && march_next) {
-            enerf_mlp32_signal_next_reduce(1);
-            signal_set = true;
-        }
-        const uint32_t overwrite = k == 0 ? 1u : 0u;
-        if (fused_mlp) {
-            STEP(enerf_nerf_mlp_backward(r.g_rgbs, r.g_sigmas, 1.0f, r.feats, r.dirs, r.rgb, a->wseg_s, a->wseg_c, a->dwseg_s,
-                                         a->dwseg_c, a->w0_cols_c, overwrite, r.M, a->out_c, r.dfeat, 1, s));
-        } else {
-            enerf_mlp32_defer_reduce(1);
-            defer_set = true;
-            STEP(enerf_mlp32_backward_p(r.g_rgbs, r.h32, a->wseg_c, a->dwseg_c, a->w0_cols_c, 1, overwrite, r.fb_c, r.M, 32,
-                                        a->out_c, a->nh_c, 0, nullptr, r.dx32, 0, 0, r.rgb, a->out_c, nullptr, nullptr, 0, s));
-            STEP(enerf_mlp32_backward_p(r.dx32, r.feats, a->wseg_s, a->dwseg_s, 32, 0, overwrite, r.fb_s, r.M, 32, 16, a->nh_s,
-                                        0, nullptr, r.dfeat, 1, 32, nullptr, 0, r.g_sigmas, r.h32, 32, s));
-            enerf_mlp32_defer_reduce(0);
-            defer_set = false;
-        }
-        if (rows_set) {
-            enerf_mlp32_valid_rows(nullptr);
-            rows_set = false;
-        }
-        if (k == 1 && march_next) {
-            // the next step's two marches, on the side stream, behind this step's last MLP backward
-            enerf_mlp32_signal_next_reduce(0);
-            signal_set = false;
-            enerf_stream_t ss = a->side_stream;
-            STEP(enerf_stream_wait_mlp32_signal(ss));
-            for (int q = 0; q < 2; q++) {
-                const enerf_step_render& n = a->r[q];
-                if (!n.next_rays_o) continue;
-                STEP(enerf_march_fuse_near_far(a->aabb, a->min_near));       // (near / far inside the march's count pass)
-                STEP(enerf_march_rays_train_ex(n.next_rays_o, n.next_rays_d, a->bitfield, a->bound, a->dt_gamma,
-                                               a->max_steps, n.next_N, a->cascade, a->grid_size, n.next_M, n.next_nears,
-                                               n.next_fars, n.next_xyzs, n.next_dirs, n.next_deltas, n.next_rays,
-                                               n.next_counter, a->perturb, a->march_flags, ss));
-            }
-        }
-        grid_valid_rows(r.counter, 0, 0);
-        STEP(enerf_grid_encode_backward_ex(r.dfeat, r.xyzs, a->embeddings, a->offsets, a->table_grad, r.M, 3, 2, 16,
-                                           a->level_scale_log2, a->base_resolution, 0, r.dfeat, r.dfeat, a->gridtype,
-                                           ENERF_F32, 2, in_add, in_mul, 1, total, s));
+    if (int rc = event_loss(a)) return rc;
+    for (uint32_t k = 0; k < 2; k++) {
+        if (int rc = blend_backward(a, a->r[k], b[k].sigma, b[k].rgb, b[k].g_sigmas, b[k].g_rgbs)) return rc;
+        // the next step's marches, on the side stream, behind this step's last MLP backward
+        const bool side = k == 1 && n_next;
+        if (int rc = backward(st, a, b[k], side, false)) return rc;
+        if (side)
+            if (int rc = marches_side(st, a, next, n_next)) return rc;
+        if (int rc = table_backward(st, a, b[k], 1)) return rc;
     }
-    STEP(enerf_grid_adam_from_records_ex(a->table, a->table_grad, a->table_m, a->table_v, a->offsets, 16, 2, a->lr,
-                                         a->beta1, a->beta2, a->eps, a->table_step, a->n_small, a->small_p, a->small_g,
-                                         a->small_m, a->small_v, a->small_n, a->small_lr, a->small_step, s));
-done:
-#undef STEP
-    // (one-shot march requests never outlive the step they were armed for -- csrc/raymarching.hip: MarchOneShot)
-    enerf_march_fuse_near_far(nullptr, 0.0f);
-    enerf_march_mirror_count(nullptr);
-    grid_valid_rows(nullptr, 0, 0);
-    if (defer_set) enerf_mlp32_defer_reduce(0);
-    if (signal_set) enerf_mlp32_signal_next_reduce(0);
-    if (rows_set) enerf_mlp32_valid_rows(nullptr);
-    if (prev_prec >= 0) enerf_mlp32_precision(prev_prec);
-    return rc;
+    return optimizer(st, a, "train_step_events");
 }
 
 extern "C" int enerf_debug_fold_reduce(int on) {

@@ -567,39 +567,58 @@ def train_step_mse(model, rays_o, rays_d, target, bg_color=1, perturb=True, dt_g
 
 
 # ---------------------------------------------------------------------------------------------------------------------
-# The closed-form RGB step as ONE library call (csrc/train_step.hip: enerf_train_step_mse).  The same entry points in the
-# same order as train_step_mse above + FusedAdam.step_grid_table, issued by the library itself: what is left on this
-# side is the bookkeeping (stage hand-over, buffers, optimizer step counts).
+# The closed-form steps as ONE library call each (csrc/train_step.hip: enerf_train_step_mse, enerf_train_step_events).  The
+# same entry points in the same order as train_step_mse above / events.train_step_events_manual + FusedAdam.step_grid_table,
+# issued by the library itself: what is left on this side is the bookkeeping (stage hand-over, buffers, optimizer step
+# counts), written once for both steps.
 import ctypes as _ct
 
 NATIVE_STEP = _os.environ.get("ENERF_NATIVE_STEP", "1") != "0"
 _vp, _u32, _f32c = _ct.c_void_p, _ct.c_uint32, _ct.c_float
 
 
-class _StepArgs(_ct.Structure):          # enerf_train_step_args (include/enerf_hip.h), field for field
-    _fields_ = ([("struct_bytes", _u32), ("mlp_precision", _ct.c_int), ("stream", _vp), ("side_stream", _vp),
-                 ("N", _u32), ("M", _u32)]
-                + [(n, _vp) for n in ("xyzs", "dirs", "deltas", "rays", "counter", "target")]
-                + [("bg_scalar", _f32c), ("grad_scale", _f32c), ("loss", _vp), ("embeddings", _vp), ("offsets", _vp),
-                   ("level_scale_log2", _f32c), ("bound", _f32c), ("inv_two_bound", _f32c), ("base_resolution", _u32),
-                   ("gridtype", _u32)]
-                + [(n, _vp) for n in ("wseg_s", "wseg_c", "dwseg_s", "dwseg_c")]
-                + [(n, _u32) for n in ("nh_s", "nh_c", "w0_cols_c", "out_c")]
-                + [(n, _vp) for n in ("feats", "h32", "fb_s", "fb_c", "sigma", "rgb", "weights_sum", "image", "out_image",
-                                      "g_sigmas", "g_rgbs", "dx32", "dfeat")]
-                + [(n, _vp) for n in ("next_rays_o", "next_rays_d", "aabb", "bitfield")]
-                + [("min_near", _f32c), ("dt_gamma", _f32c)]
-                + [(n, _u32) for n in ("next_N", "next_M", "cascade", "grid_size", "max_steps", "perturb", "march_flags")]
-                + [(n, _vp) for n in ("next_nears", "next_fars", "next_xyzs", "next_dirs", "next_deltas", "next_rays",
-                                      "next_counter")]
-                + [(n, _vp) for n in ("table", "table_grad", "table_m", "table_v")]
-                + [(n, _f32c) for n in ("lr", "beta1", "beta2", "eps")]
-                + [("table_step", _u32), ("n_small", _u32)]
-                + [(n, _vp) for n in ("small_p", "small_g", "small_m", "small_v", "small_n", "small_lr", "small_step")]
-                + [("flags", _u32), ("reserved", _u32)])
+def _fields(ctype, *names):
+    return [(n, ctype) for n in names]
+
+
+# The blocks of enerf_train_step_args / enerf_step_render / enerf_event_step_args (include/enerf_hip.h), each named once
+_MLP_SCRATCH = ("feats", "h32", "fb_s", "fb_c", "sigma", "rgb", "g_sigmas", "g_rgbs", "dx32", "dfeat")
+_NEXT_BUFS = ("nears", "fars", "xyzs", "dirs", "deltas", "rays", "counter")
+_SMALL = ("small_p", "small_g", "small_m", "small_v", "small_n", "small_lr", "small_step")
+_HEAD = [("struct_bytes", _u32), ("mlp_precision", _ct.c_int), ("stream", _vp), ("side_stream", _vp)]
+_SAMPLES = _fields(_u32, "N", "M") + _fields(_vp, "xyzs", "dirs", "deltas", "rays", "counter")
+_NETS = (_fields(_vp, "embeddings", "offsets") + _fields(_f32c, "level_scale_log2", "bound", "inv_two_bound")
+         + _fields(_u32, "base_resolution", "gridtype") + _fields(_vp, "wseg_s", "wseg_c", "dwseg_s", "dwseg_c")
+         + _fields(_u32, "nh_s", "nh_c", "w0_cols_c", "out_c"))
+_NEXT_RAYS, _NEXT_SIZE = _fields(_vp, "next_rays_o", "next_rays_d"), _fields(_u32, "next_N", "next_M")
+_NEXT_OUT = _fields(_vp, *("next_" + n for n in _NEXT_BUFS))
+_MARCH = _fields(_vp, "aabb", "bitfield") + _fields(_f32c, "min_near", "dt_gamma")
+_MARCH_U32 = _fields(_u32, "cascade", "grid_size", "max_steps", "perturb", "march_flags")
+_OPTIM = (_fields(_vp, "table", "table_grad", "table_m", "table_v") + _fields(_f32c, "lr", "beta1", "beta2", "eps")
+          + _fields(_u32, "table_step", "n_small") + _fields(_vp, *_SMALL) + _fields(_u32, "flags", "reserved"))
+
+
+def _scratch_fields(*images):             # a render's scratch: the MLP set with the image buffers where the header has them
+    return _fields(_vp, *_MLP_SCRATCH[:6], "weights_sum", "image", "out_image", *images, *_MLP_SCRATCH[6:])
+
+
+class _StepArgs(_ct.Structure):           # enerf_train_step_args
+    _fields_ = (_HEAD + _SAMPLES + [("target", _vp), ("bg_scalar", _f32c), ("grad_scale", _f32c), ("loss", _vp)] + _NETS
+                + _scratch_fields() + _NEXT_RAYS + _MARCH + _NEXT_SIZE + _MARCH_U32 + _NEXT_OUT + _OPTIM)
+
+
+class _StepRender(_ct.Structure):         # enerf_step_render
+    _fields_ = _SAMPLES + _scratch_fields("g_image") + _NEXT_RAYS + _NEXT_SIZE + _NEXT_OUT
+
+
+class _EventStepArgs(_ct.Structure):      # enerf_event_step_args
+    _fields_ = (_HEAD + [("r", _StepRender * 2), ("bg_color", _vp), ("pols", _vp), ("use_luma", _u32), ("linlog", _u32),
+                         ("C_thres", _f32c), ("log_thres", _f32c), ("upstream", _f32c), ("delta", _vp), ("loss", _vp)]
+                + _NETS + _MARCH + _MARCH_U32 + [("reserved0", _u32)] + _OPTIM + _fields(_vp, *("m_" + n for n in _MLP_SCRATCH)))
 
 
 COLD_NATIVE = True            # the one-call step also serves the window before the first sample budget (see cold_capacity)
+MERGE_EVENT_RENDERS = True    # the one-call event step runs both renders' samples as one batch of 2 M rows (flags bit 1)
 
 
 def cold_capacity(rows, N, max_steps, floor=0):
@@ -622,270 +641,6 @@ def native_step_supported(model, rays_o, rays_d, opt, data_parallel=False):
             and hasattr(opt, "grid_table_args") and supported(model, rays_o, rays_d, 1, 0))
 
 
-def _native_ctx(model, N, M, Nn, Mn, dev):
-    """Everything of a native step that does not change from step to step, built once per (rays, sample budget) -- i.e.
-    once per update_extra_state window: the step's scratch buffers, two sets of sample buffers for the march that runs
-    ahead (the step reads one set while the side stream fills the other), the weight / gradient pointer arrays, and the
-    argument struct with its constant fields filled in.  (20 torch.empty calls and ~60 struct fields per step otherwise:
-    most of the host's share of a step once the launches themselves come from C.)"""
-    params = fnet.network_params(model)
-    emb, weights = params[0], params[1:]
-    kind = fnet.kind_of(model)
-    arch = fnet._ARCH[kind]
-    prec = model.__dict__.get("mlp_precision")
-    prec = arch["prec"] if prec is None else int(prec)
-    out_c = weights[-1].shape[0] if kind == "linear" else 3
-    key = (N, M, Nn, Mn, kind, prec, out_c, emb.data_ptr(), tuple(w.data_ptr() for w in weights), dev)
-    ctx = model.__dict__.get("_native_ctx")
-    if ctx is not None and ctx["key"] == key:
-        return ctx
-    import numpy as _np
-    enc = model._modules["encoder"]
-    bufs = model._buffers
-    f32 = dict(dtype=torch.float32, device=dev)
-    Mp = (M + 31) // 32 * 32
-    t = dict(feats=torch.empty(16, Mp, 2, **f32), h32=torch.empty(M, 32, **f32),
-             fb_s=torch.empty(arch["nh_s"], Mp, 64, **f32), fb_c=torch.empty(arch["nh_c"], Mp, 64, **f32),
-             sigma=torch.empty(M, **f32), rgb=torch.empty(M, out_c, **f32), weights_sum=torch.empty(N, **f32),
-             image=torch.empty(N, 3, **f32), out_image=torch.empty(N, 3, **f32), g_sigmas=torch.empty(M, **f32),
-             g_rgbs=torch.empty(M, out_c, **f32), dx32=torch.empty(M, 32, **f32), dfeat=torch.empty(16, Mp, 2, **f32))
-    seg_s, seg_c = fnet._weight_segments(kind, weights)
-    dw, (dseg_s, dseg_c) = fnet._grad_segments(kind, dev, out_c)
-    grads = fnet.unpack_weight_grads(dw, out_c, kind)
-    stages = []
-    if Nn:
-        for _ in range(2):
-            stages.append(dict(nears=torch.empty(Nn, **f32), fars=torch.empty(Nn, **f32),
-                               rays=torch.empty(Nn, 3, dtype=torch.int32, device=dev), xyzs=torch.empty(Mn, 3, **f32),
-                               dirs=torch.empty(Mn, 3, **f32), deltas=torch.empty(Mn, 2, **f32), M=Mn))
-    a = _StepArgs()
-    a.struct_bytes = _ct.sizeof(_StepArgs)
-    a.mlp_precision = -1 if prec is None else prec
-    a.N, a.M = N, M
-    a.bg_scalar, a.grad_scale = 1.0, 2.0 / (3 * N)
-    a.embeddings, a.offsets = emb.data_ptr(), enc._buffers["offsets"].data_ptr()
-    a.level_scale_log2 = float(_np.log2(enc.per_level_scale))
-    a.bound, a.inv_two_bound = float(model.bound), float(_np.float32(1.0) / _np.float32(2 * model.bound))
-    a.base_resolution, a.gridtype = int(enc.base_resolution), int(enc.gridtype_id)
-    a.wseg_s, a.wseg_c = _ct.cast(seg_s, _vp), _ct.cast(seg_c, _vp)
-    a.dwseg_s, a.dwseg_c = _ct.cast(dseg_s, _vp), _ct.cast(dseg_c, _vp)
-    a.nh_s, a.nh_c, a.w0_cols_c, a.out_c = arch["nh_s"], arch["nh_c"], arch["w0c"], out_c
-    for name, buf in t.items():
-        setattr(a, name, buf.data_ptr())
-    a.aabb, a.bitfield = bufs["aabb_train"].data_ptr(), bufs["density_bitfield"].data_ptr()
-    a.min_near = float(model.min_near)
-    a.cascade, a.grid_size = int(model.cascade), int(model.grid_size)
-    a.table = emb.data_ptr()
-    ctx = dict(key=key, t=t, seg=(seg_s, seg_c), dseg=(dseg_s, dseg_c), dw=dw, grads=grads, stages=stages, flip=0, a=a,
-               emb=emb, weights=weights, out_image=t["out_image"], kind=kind, out_c=out_c)
-    model.__dict__["_native_ctx"] = ctx
-    return ctx
-
-
-def train_step_native(model, rays_o, rays_d, target, opt, next_rays=None, side_stream=None, loss_out=None, perturb=True,
-                      dt_gamma=0, max_steps=1024, raw=False, defer_dp=False):
-    """One closed-form RGB step (loss = mean((image - target)^2), white background) through enerf_train_step_mse:
-    render of this batch (marched ahead of time when the previous step asked for it) + backward + the optimizer, and the
-    march of `next_rays` = (rays_o, rays_d) on `side_stream` behind the MLP backward.  -> blended image [N,3] (a buffer
-    that the next step of the same shape overwrites).  Gradients of the MLP weights are left in p.grad (views of one flat
-    buffer, likewise reused), the table's dense gradient buffer comes back clean; the optimizer's step counts advance.
-    raw=True (data parallel): the table's gradient is summed into the dense buffer `embeddings.grad` and NO optimizer
-    runs -- -> (image, flat MLP dW buffer); the caller averages both over the ranks and steps the optimizer."""
-    rays_o = rays_o.contiguous().view(-1, 3)
-    rays_d = rays_d.contiguous().view(-1, 3)
-    N, dev = rays_o.shape[0], rays_o.device
-    with torch.no_grad():
-        pre = _take_premarched(model, rays_o, rays_d, perturb, dt_gamma, max_steps, defer_cold_check=True)
-        if pre is not None:
-            model.rendered_counter_slot = pre["slot"]
-        else:
-            counter = _next_counter(model)
-            model.rendered_counter_slot = getattr(model, "last_counter_slot", None)
-            pre = march_stage(model, rays_o, rays_d, counter, _budget(model), bool(perturb), False, float(dt_gamma),
-                              int(max_steps))
-        nxt_ok = cold_next = False
-        Nn = Mn = 0
-        no = nd = None
-        if next_rays is not None and side_stream is not None:
-            no, nd = next_rays[0].contiguous().view(-1, 3), next_rays[1].contiguous().view(-1, 3)
-            stash = getattr(model, "_premarched", None)
-            if not isinstance(stash, dict):
-                stash = model._premarched = {}
-            if not any("pending" in p for p in stash.values()):
-                nxt_ok = True
-                Nn = no.shape[0]
-                mc = _budget(model)
-                cold_next = mc <= 0
-                if cold_next:                    # cold window: rows reserved from the last render whose count is known
-                    Mn = model._cold_cap = cold_capacity(int(model._cold_rows), Nn, int(max_steps),
-                                                         int(getattr(model, "_cold_cap", 0)))
-                else:
-                    Mn = mc + (128 - mc % 128)
-        nxt_counter = nxt_slot = None
-        if nxt_ok:
-            nxt_counter = _next_counter(model)
-            nxt_slot = getattr(model, "last_counter_slot", None)
-
-        def prepare(pre):
-            M = pre["M"]
-            ctx = _native_ctx(model, N, M, Nn, Mn, dev)
-            a, emb, weights, grads = ctx["a"], ctx["emb"], ctx["weights"], ctx["grads"]
-            if emb.grad is None:                    # the dense part of the table's gradient (levels too small to bin)
-                emb.grad = torch.zeros_like(emb)
-            a.stream = L.stream_handle()
-            a.xyzs, a.dirs, a.deltas = pre["xyzs"].data_ptr(), pre["dirs"].data_ptr(), pre["deltas"].data_ptr()
-            a.rays = pre["rays"].data_ptr()
-            a.counter = pre["counter"].data_ptr() if SKIP_PADDING_ROWS else None
-            a.target = target.contiguous().view(-1, 3).data_ptr()
-            a.loss = None if loss_out is None else loss_out.data_ptr()
-            # (bit 1: the sharded tail with an owner range set -- this rank's slice of the table stays as record lists)
-            a.flags = (3 if defer_dp else 1) if raw else 0
-            # the next batch's march: kernels on the side stream, into the buffer set the current batch is NOT using
-            nxt = key = None
-            a.next_rays_o = None
-            if nxt_ok:
-                st_bufs = ctx["stages"][ctx["flip"]]
-                if any(pre[k] is st_bufs[k] for k in ("xyzs", "rays")):
-                    st_bufs = ctx["stages"][ctx["flip"] ^ 1]
-                    which = ctx["flip"] ^ 1
-                else:
-                    which = ctx["flip"]
-                nxt = _Stage(st_bufs)
-                nxt["counter"] = nxt_counter
-                nxt["slot"] = nxt_slot
-                nxt["_which"] = which
-                a.side_stream = side_stream.cuda_stream
-                a.next_rays_o, a.next_rays_d = no.data_ptr(), nd.data_ptr()
-                a.dt_gamma = float(dt_gamma)
-                a.next_N, a.next_M, a.max_steps = Nn, Mn, int(max_steps)
-                a.perturb = 1 if perturb else 0
-                # (bit 4: this march stays on the side stream -- the cold window reads its count back behind it there)
-                a.march_flags = occupied_box_flag(model) | 3 | 8 | (16 if cold_next else 0)
-                for name in ("nears", "fars", "xyzs", "dirs", "deltas", "rays", "counter"):
-                    setattr(a, "next_" + name, nxt[name].data_ptr())
-                key = (no.data_ptr(), nd.data_ptr(), Nn, bool(perturb), float(dt_gamma), int(max_steps))
-            a.table_grad = emb.grad.data_ptr()
-            if raw:
-                a.n_small = 0
-                ctx["plan"] = None                  # (a later optimizer-carrying step rebuilds its arrays)
-            else:
-                plan = ctx.get("plan")
-                if plan is None or ctx.get("plan_opt") is not opt:
-                    # the optimizer's host arrays (pointers, sizes, learning rates, step counts of the MLP weights): built once
-                    plan = ctx["plan"] = opt.grid_table_plan(emb, list(weights), list(grads))
-                    ctx["plan_opt"] = opt
-                    small = plan.arrays
-                    st = plan.state
-                    a.table_m, a.table_v = st["exp_avg"].data_ptr(), st["exp_avg_sq"].data_ptr()
-                    a.n_small = small[0]
-                    for name, arr in zip(("small_p", "small_g", "small_m", "small_v", "small_n", "small_lr", "small_step"),
-                                         small[1:]):
-                        setattr(a, name, _ct.cast(arr, _vp) if arr is not None else None)
-            return ctx, a, nxt, key, M
-
-        ctx, a, nxt, key, M = prepare(pre)
-        if "cold_check" in pre:
-            # everything above was host work that did not need the count; only now is it waited for
-            fixed = _check_cold_stage(model, pre, rays_o, rays_d, perturb, dt_gamma, max_steps)
-            if fixed is not pre:
-                pre = fixed
-                ctx, a, nxt, key, M = prepare(pre)
-        emb, weights, grads = ctx["emb"], ctx["weights"], ctx["grads"]
-        which = 0
-        if nxt is not None:
-            which = nxt.pop("_which")
-            ctx["flip"] = which ^ 1              # (the set the next call looks at first is the one this stage does not use)
-        if not raw:
-            a.lr, a.beta1, a.beta2, a.eps, a.table_step = ctx["plan"]()
-        cold_host = None
-        if nxt is not None and cold_next and MIRROR_COUNT:
-            # the cold window's next march writes its count straight into pinned host memory (enerf_march_mirror_count)
-            hosts = ctx.get("cold_hosts")
-            if hosts is None:
-                hosts = ctx["cold_hosts"] = [torch.empty(2, dtype=torch.int32, pin_memory=True) for _ in range(2)]
-            cold_host = hosts[which]
-            cold_host.fill_(-1)               # (what _check_cold_stage watches for: both words are >= 0 once the count has landed)
-            L.check(L.lib().enerf_march_mirror_count(cold_host.data_ptr()), "march_mirror_count")
-        carried_before = L.lib().enerf_debug_carry_count(-2) if nxt is not None else 0
-        L.check(L.lib().enerf_train_step_mse(_ct.byref(a)), "train_step_mse")
-        # (the next batch's march may have ridden in this call's own launches, on this stream: no event to wait for then)
-        march_carried = nxt is not None and L.lib().enerf_debug_carry_count(-2) != carried_before
-        # (the launch counters bench.py reads: the library issued one grid_encode_forward / backward over M points)
-        from .backends import _gridencoder as _gbk
-        _gbk.STATS["fwd_points"] += M
-        _gbk.STATS["budget_rows"] += M
-        _gbk.STATS["fwd_calls"] += 1
-        _gbk.STATS["bwd_points"] += M
-        _gbk.STATS["bwd_calls"] += 1
-        _gbk.LIFETIME["fwd_points"] += M
-        _gbk.LIFETIME["fwd_calls"] += 1
-        if nxt is not None:
-            if cold_next:
-                # the count of the march just queued travels to pinned memory behind it (one slot per stage set)
-                hosts = ctx.get("cold_hosts")
-                if hosts is None:
-                    hosts = ctx["cold_hosts"] = [torch.empty(2, dtype=torch.int32, pin_memory=True) for _ in range(2)]
-                host = hosts[which]
-                with torch.cuda.stream(side_stream):
-                    if cold_host is None:
-                        host.fill_(-1)            # (what _check_cold_stage watches for: both words are >= 0 once the copy has landed)
-                        host.copy_(nxt["counter"], non_blocking=True)
-                    done = torch.cuda.Event()
-                    done.record(side_stream)
-                nxt["cold_check"] = (done, host, Mn)
-                nxt["ready"] = done
-            elif march_carried:
-                nxt["ready"] = None                  # (marched on this very stream)
-            else:
-                nxt["ready"] = torch.cuda.Event()
-                nxt["ready"].record(side_stream)
-            stash[key] = nxt
-            model._last_march_event = None if march_carried else (nxt["ready"], side_stream)
-        if not raw:
-            views = ctx.get("grad_views")
-            if views is None:
-                views = ctx["grad_views"] = [g.view_as(p) for p, g in zip(weights, grads)]
-            for p, g in zip(weights, views):
-                if p.grad is not g:
-                    p.grad = g
-    return (ctx["out_image"], ctx["dw"]) if raw else ctx["out_image"]
-
-
-# ---------------------------------------------------------------------------------------------------------------------
-# The event-only step (two renders, event loss, one optimizer pass) as ONE library call: csrc/train_step.hip
-# enerf_train_step_events -- events.train_step_events_manual + FusedAdam.step_grid_table, call for call.
-class _StepRender(_ct.Structure):         # enerf_step_render
-    _fields_ = ([("N", _u32), ("M", _u32)]
-                + [(n, _vp) for n in ("xyzs", "dirs", "deltas", "rays", "counter")]
-                + [(n, _vp) for n in ("feats", "h32", "fb_s", "fb_c", "sigma", "rgb", "weights_sum", "image", "out_image",
-                                      "g_image", "g_sigmas", "g_rgbs", "dx32", "dfeat")]
-                + [("next_rays_o", _vp), ("next_rays_d", _vp), ("next_N", _u32), ("next_M", _u32)]
-                + [(n, _vp) for n in ("next_nears", "next_fars", "next_xyzs", "next_dirs", "next_deltas", "next_rays",
-                                      "next_counter")])
-
-
-class _EventStepArgs(_ct.Structure):      # enerf_event_step_args
-    _fields_ = ([("struct_bytes", _u32), ("mlp_precision", _ct.c_int), ("stream", _vp), ("side_stream", _vp),
-                 ("r", _StepRender * 2), ("bg_color", _vp), ("pols", _vp), ("use_luma", _u32), ("linlog", _u32),
-                 ("C_thres", _f32c), ("log_thres", _f32c), ("upstream", _f32c), ("delta", _vp), ("loss", _vp),
-                 ("embeddings", _vp), ("offsets", _vp), ("level_scale_log2", _f32c), ("bound", _f32c),
-                 ("inv_two_bound", _f32c), ("base_resolution", _u32), ("gridtype", _u32)]
-                + [(n, _vp) for n in ("wseg_s", "wseg_c", "dwseg_s", "dwseg_c")]
-                + [(n, _u32) for n in ("nh_s", "nh_c", "w0_cols_c", "out_c")]
-                + [("aabb", _vp), ("bitfield", _vp), ("min_near", _f32c), ("dt_gamma", _f32c)]
-                + [(n, _u32) for n in ("cascade", "grid_size", "max_steps", "perturb", "march_flags", "reserved0")]
-                + [(n, _vp) for n in ("table", "table_grad", "table_m", "table_v")]
-                + [(n, _f32c) for n in ("lr", "beta1", "beta2", "eps")]
-                + [("table_step", _u32), ("n_small", _u32)]
-                + [(n, _vp) for n in ("small_p", "small_g", "small_m", "small_v", "small_n", "small_lr", "small_step")]
-                + [("flags", _u32), ("reserved", _u32)]
-                + [(n, _vp) for n in ("m_feats", "m_h32", "m_fb_s", "m_fb_c", "m_sigma", "m_rgb", "m_g_sigmas", "m_g_rgbs",
-                                      "m_dx32", "m_dfeat")])
-
-
-MERGE_EVENT_RENDERS = True    # the one-call event step runs both renders' samples as one batch of 2 M rows (flags bit 1)
-
-
 def native_events_supported(model, data, loss_opt, opt):
     """What enerf_train_step_events serves: the steady state (a sample budget exists) of the event-only step with the
     fused loss kernel (C_thres != -1, fp32, one background colour: a batch of one image), unit density scale, the fused
@@ -902,7 +657,13 @@ def native_events_supported(model, data, loss_opt, opt):
                           data["rays_evs_d2"].contiguous().view(-1, 3), 1, 0))
 
 
-def _native_events_ctx(model, N, Ms, Nn, Mn, luma, dev):
+# ---- what a context holds: everything of a native step that does not change from step to step, built once per (rays,
+# sample budget) -- i.e. once per update_extra_state window: the step's scratch buffers, two sets of sample buffers for the
+# march that runs ahead (the step reads one set while the next march fills the other), the weight / gradient pointer arrays,
+# and the argument struct with its constant fields filled in.  (20 torch.empty calls and ~60 struct fields per step
+# otherwise: most of the host's share of a step once the launches themselves come from C.)
+def _ctx_for(model, attr, struct, sizes, dev):
+    """-> (context, whether it was just built with only the shared parts in it).  Keyed by `sizes` and the networks."""
     params = fnet.network_params(model)
     emb, weights = params[0], params[1:]
     kind = fnet.kind_of(model)
@@ -910,70 +671,18 @@ def _native_events_ctx(model, N, Ms, Nn, Mn, luma, dev):
     prec = model.__dict__.get("mlp_precision")
     prec = arch["prec"] if prec is None else int(prec)
     out_c = weights[-1].shape[0] if kind == "linear" else 3
-    key = (N, Ms, Nn, Mn, kind, prec, out_c, luma, emb.data_ptr(), tuple(w.data_ptr() for w in weights), dev)
-    ctx = model.__dict__.get("_native_events_ctx")
+    key = sizes + (kind, prec, out_c, emb.data_ptr(), tuple(w.data_ptr() for w in weights), dev)
+    ctx = model.__dict__.get(attr)
     if ctx is not None and ctx["key"] == key:
-        return ctx
+        return ctx, False
     import numpy as _np
     enc = model._modules["encoder"]
     bufs = model._buffers
-    f32 = dict(dtype=torch.float32, device=dev)
     seg_s, seg_c = fnet._weight_segments(kind, weights)
     dw, (dseg_s, dseg_c) = fnet._grad_segments(kind, dev, out_c)
-    grads = fnet.unpack_weight_grads(dw, out_c, kind)
-    a = _EventStepArgs()
-    a.struct_bytes = _ct.sizeof(_EventStepArgs)
+    a = struct()
+    a.struct_bytes = _ct.sizeof(struct)
     a.mlp_precision = -1 if prec is None else prec
-    ts, stages, pair_bufs = [], [], []
-    tm = None
-    if MERGE_EVENT_RENDERS and Ms[0] == Ms[1]:
-        M2 = 2 * Ms[0]                                  # (2 M is a multiple of 256: no extra padding of the level-major rows)
-        tm = dict(m_feats=torch.empty(16, M2, 2, **f32), m_h32=torch.empty(M2, 32, **f32),
-                  m_fb_s=torch.empty(arch["nh_s"], M2, 64, **f32), m_fb_c=torch.empty(arch["nh_c"], M2, 64, **f32),
-                  m_sigma=torch.empty(M2, **f32), m_rgb=torch.empty(M2, out_c, **f32), m_g_sigmas=torch.empty(M2, **f32),
-                  m_g_rgbs=torch.empty(M2, out_c, **f32), m_dx32=torch.empty(M2, 32, **f32),
-                  m_dfeat=torch.empty(16, M2, 2, **f32))
-        for name, buf in tm.items():
-            setattr(a, name, buf.data_ptr())
-    for q, M in enumerate(Ms):
-        Mp = (M + 31) // 32 * 32
-        if tm is not None:
-            # the per-render scratch (steps whose two stages were not marched together: right after an update) is the two
-            # halves of the merged allocations, each half in the per-render shape: no second set of buffers
-            def half(name, *shape):
-                flat = tm["m_" + name].view(-1)
-                n = flat.numel() // 2
-                return flat[q * n:(q + 1) * n].view(*shape)
-            t = dict(feats=half("feats", 16, Mp, 2), h32=half("h32", M, 32), fb_s=half("fb_s", arch["nh_s"], Mp, 64),
-                     fb_c=half("fb_c", arch["nh_c"], Mp, 64), sigma=half("sigma", M), rgb=half("rgb", M, out_c),
-                     g_sigmas=half("g_sigmas", M), g_rgbs=half("g_rgbs", M, out_c), dx32=half("dx32", M, 32),
-                     dfeat=half("dfeat", 16, Mp, 2))
-        else:
-            t = dict(feats=torch.empty(16, Mp, 2, **f32), h32=torch.empty(M, 32, **f32),
-                     fb_s=torch.empty(arch["nh_s"], Mp, 64, **f32), fb_c=torch.empty(arch["nh_c"], Mp, 64, **f32),
-                     sigma=torch.empty(M, **f32), rgb=torch.empty(M, out_c, **f32), g_sigmas=torch.empty(M, **f32),
-                     g_rgbs=torch.empty(M, out_c, **f32), dx32=torch.empty(M, 32, **f32), dfeat=torch.empty(16, Mp, 2, **f32))
-        t.update(weights_sum=torch.empty(N, **f32), image=torch.empty(N, 3, **f32), out_image=torch.empty(N, 3, **f32),
-                 g_image=torch.empty(N, 3, **f32))
-        ts.append(t)
-        a.r[q].N, a.r[q].M = N, M
-        for name, buf in t.items():
-            setattr(a.r[q], name, buf.data_ptr())
-        sets = []
-        if Nn:
-            for f in range(2):
-                # the two renders' sample buffers of one stage generation are the halves of ONE allocation: a step that
-                # consumes both finds the second render's rows right behind the first's M (merged layout, see below)
-                if q == 0:
-                    pair_bufs.append(dict(xyzs=torch.empty(2 * Mn, 3, **f32), dirs=torch.empty(2 * Mn, 3, **f32),
-                                          deltas=torch.empty(2 * Mn, 2, **f32)))
-                pb = pair_bufs[f]
-                sets.append(dict(nears=torch.empty(Nn, **f32), fars=torch.empty(Nn, **f32),
-                                 rays=torch.empty(Nn, 3, dtype=torch.int32, device=dev), xyzs=pb["xyzs"][q * Mn:(q + 1) * Mn],
-                                 dirs=pb["dirs"][q * Mn:(q + 1) * Mn], deltas=pb["deltas"][q * Mn:(q + 1) * Mn], M=Mn))
-        stages.append(sets)
-    delta = torch.empty(1, N, 1 if luma else 3, **f32)
-    a.delta = delta.data_ptr()
     a.embeddings, a.offsets = emb.data_ptr(), enc._buffers["offsets"].data_ptr()
     a.level_scale_log2 = float(_np.log2(enc.per_level_scale))
     a.bound, a.inv_two_bound = float(model.bound), float(_np.float32(1.0) / _np.float32(2 * model.bound))
@@ -985,10 +694,286 @@ def _native_events_ctx(model, N, Ms, Nn, Mn, luma, dev):
     a.min_near = float(model.min_near)
     a.cascade, a.grid_size = int(model.cascade), int(model.grid_size)
     a.table = emb.data_ptr()
-    ctx = dict(key=key, t=ts, tm=tm, seg=(seg_s, seg_c), dseg=(dseg_s, dseg_c), dw=dw, grads=grads, stages=stages,
-               flip=[0, 0], a=a, emb=emb, weights=weights, delta=delta, kind=kind, out_c=out_c)
-    model.__dict__["_native_events_ctx"] = ctx
+    ctx = dict(key=key, seg=(seg_s, seg_c), dseg=(dseg_s, dseg_c), dw=dw, grads=fnet.unpack_weight_grads(dw, out_c, kind),
+               a=a, emb=emb, weights=weights, kind=kind, arch=arch, out_c=out_c)
+    model.__dict__[attr] = ctx
+    return ctx, True
+
+
+def _mlp_scratch(rows, arch, out_c, new):
+    """The scratch of `rows` rows through the networks (enerf_hip.h: feats .. dfeat); new(name, *shape) -> the tensor."""
+    Mp = (rows + 31) // 32 * 32
+    shapes = dict(feats=(16, Mp, 2), h32=(rows, 32), fb_s=(arch["nh_s"], Mp, 64), fb_c=(arch["nh_c"], Mp, 64), sigma=(rows,),
+                  rgb=(rows, out_c), g_sigmas=(rows,), g_rgbs=(rows, out_c), dx32=(rows, 32), dfeat=(16, Mp, 2))
+    return {name: new(name, *shape) for name, shape in shapes.items()}
+
+
+def _stage_set(Nn, Mn, f32, dev, samples=None):
+    """One set of buffers a march of Nn rays into Mn rows fills (`samples`: its xyzs / dirs / deltas, where they exist)."""
+    if samples is None:
+        samples = dict(xyzs=torch.empty(Mn, 3, **f32), dirs=torch.empty(Mn, 3, **f32), deltas=torch.empty(Mn, 2, **f32))
+    return dict(nears=torch.empty(Nn, **f32), fars=torch.empty(Nn, **f32),
+                rays=torch.empty(Nn, 3, dtype=torch.int32, device=dev), M=Mn, **samples)
+
+
+def _native_ctx(model, N, M, Nn, Mn, dev):
+    ctx, new = _ctx_for(model, "_native_ctx", _StepArgs, (N, M, Nn, Mn), dev)
+    if not new:
+        return ctx
+    f32 = dict(dtype=torch.float32, device=dev)
+    a = ctx["a"]
+    t = _mlp_scratch(M, ctx["arch"], ctx["out_c"], lambda name, *shape: torch.empty(*shape, **f32))
+    t.update(weights_sum=torch.empty(N, **f32), image=torch.empty(N, 3, **f32), out_image=torch.empty(N, 3, **f32))
+    for name, buf in t.items():
+        setattr(a, name, buf.data_ptr())
+    a.N, a.M = N, M
+    a.bg_scalar, a.grad_scale = 1.0, 2.0 / (3 * N)
+    ctx.update(t=t, stages=[_stage_set(Nn, Mn, f32, dev) for _ in range(2)] if Nn else [], flip=0,
+               out_image=t["out_image"])
     return ctx
+
+
+def _native_events_ctx(model, N, Ms, Nn, Mn, luma, dev):
+    ctx, new = _ctx_for(model, "_native_events_ctx", _EventStepArgs, (N, Ms, Nn, Mn, luma), dev)
+    if not new:
+        return ctx
+    f32 = dict(dtype=torch.float32, device=dev)
+    a, arch, out_c = ctx["a"], ctx["arch"], ctx["out_c"]
+    fresh = lambda name, *shape: torch.empty(*shape, **f32)
+    tm = None
+    if MERGE_EVENT_RENDERS and Ms[0] == Ms[1]:
+        tm = _mlp_scratch(2 * Ms[0], arch, out_c, fresh)     # (2 M is a multiple of 256: no padding of the level-major rows)
+        for name, buf in tm.items():
+            setattr(a, "m_" + name, buf.data_ptr())
+    # the two renders' sample buffers of one stage generation are the halves of ONE allocation: a step that consumes both
+    # finds the second render's rows right behind the first's M (merged layout, see train_step_events_native)
+    pairs = [dict(xyzs=torch.empty(2 * Mn, 3, **f32), dirs=torch.empty(2 * Mn, 3, **f32), deltas=torch.empty(2 * Mn, 2, **f32))
+             for _ in range(2 if Nn else 0)]
+    ts, stages = [], []
+    for q, M in enumerate(Ms):
+        def half(name, *shape):
+            # the per-render scratch (steps whose two stages were not marched together: right after an update) is the two
+            # halves of the merged allocations, each half in the per-render shape: no second set of buffers
+            flat = tm[name].view(-1)
+            n = flat.numel() // 2
+            return flat[q * n:(q + 1) * n].view(*shape)
+        t = _mlp_scratch(M, arch, out_c, fresh if tm is None else half)
+        t.update(weights_sum=torch.empty(N, **f32), image=torch.empty(N, 3, **f32), out_image=torch.empty(N, 3, **f32),
+                 g_image=torch.empty(N, 3, **f32))
+        ts.append(t)
+        a.r[q].N, a.r[q].M = N, M
+        for name, buf in t.items():
+            setattr(a.r[q], name, buf.data_ptr())
+        stages.append([_stage_set(Nn, Mn, f32, dev, {k: v[q * Mn:(q + 1) * Mn] for k, v in pb.items()}) for pb in pairs])
+    delta = torch.empty(1, N, 1 if luma else 3, **f32)
+    a.delta = delta.data_ptr()
+    ctx.update(t=ts, tm=tm, stages=stages, flip=[0, 0], delta=delta)
+    return ctx
+
+
+# ---- the per-step bookkeeping both drivers share
+def _take_or_march(model, rays_o, rays_d, perturb, dt_gamma, max_steps, defer_cold_check=False):
+    """The batch's samples: the stage marched ahead for these rays, or a march now."""
+    pre = _take_premarched(model, rays_o, rays_d, perturb, dt_gamma, max_steps, defer_cold_check=defer_cold_check)
+    if pre is not None:
+        model.rendered_counter_slot = pre["slot"]
+        return pre
+    counter = _next_counter(model)
+    model.rendered_counter_slot = getattr(model, "last_counter_slot", None)
+    return march_stage(model, rays_o, rays_d, counter, _budget(model), bool(perturb), False, float(dt_gamma), int(max_steps))
+
+
+def _stash_if_free(model):
+    """The stash the next stages go into, or None while an unbudgeted stage waits there for its write pass (see
+    prefetch_march: nothing else may be marched then)."""
+    stash = getattr(model, "_premarched", None)
+    if not isinstance(stash, dict):
+        stash = model._premarched = {}
+    return None if any("pending" in p for p in stash.values()) else stash
+
+
+def _fill_step(ctx, a):
+    emb = ctx["emb"]
+    if emb.grad is None:                    # the dense part of the table's gradient (levels too small to bin)
+        emb.grad = torch.zeros_like(emb)
+    a.stream = L.stream_handle()
+    a.table_grad = emb.grad.data_ptr()
+
+
+def _fill_samples(r, pre):
+    r.xyzs, r.dirs, r.deltas = pre["xyzs"].data_ptr(), pre["dirs"].data_ptr(), pre["deltas"].data_ptr()
+    r.rays = pre["rays"].data_ptr()
+    r.counter = pre["counter"].data_ptr() if SKIP_PADDING_ROWS else None
+    r.next_rays_o = None
+
+
+def _fill_march(a, model, side_stream, perturb, dt_gamma, max_steps, more_flags=0):
+    a.side_stream = side_stream.cuda_stream
+    a.dt_gamma, a.max_steps, a.perturb = float(dt_gamma), int(max_steps), 1 if perturb else 0
+    a.march_flags = occupied_box_flag(model) | 3 | 8 | more_flags
+
+
+def _next_stage(r, sets, flip, pre, counter, slot, no, nd):
+    """The next march of (no, nd) into the buffer set the current batch `pre` is NOT using (sets[flip] is looked at first),
+    described in r's next_* fields -> (the stage, its set's index: the next call looks at the other one first)."""
+    which = flip ^ 1 if any(pre[k] is sets[flip][k] for k in ("xyzs", "rays")) else flip
+    nxt = _Stage(sets[which])
+    nxt["counter"], nxt["slot"] = counter, slot
+    r.next_rays_o, r.next_rays_d, r.next_N, r.next_M = no.data_ptr(), nd.data_ptr(), no.shape[0], nxt["M"]
+    for name in _NEXT_BUFS:
+        setattr(r, "next_" + name, nxt[name].data_ptr())
+    return nxt, which
+
+
+def _stage_key(no, nd, perturb, dt_gamma, max_steps):
+    return (no.data_ptr(), nd.data_ptr(), no.shape[0], bool(perturb), float(dt_gamma), int(max_steps))
+
+
+def _fill_optimizer(ctx, a, opt):
+    """The optimizer block: host arrays (pointers, sizes, learning rates, step counts of the MLP weights) built once per
+    context and optimizer, the scalars of this step (which advances the step counts)."""
+    plan = ctx.get("plan")
+    if plan is None or ctx.get("plan_opt") is not opt:
+        plan = ctx["plan"] = opt.grid_table_plan(ctx["emb"], list(ctx["weights"]), list(ctx["grads"]))
+        ctx["plan_opt"] = opt
+        st = plan.state
+        a.table_m, a.table_v = st["exp_avg"].data_ptr(), st["exp_avg_sq"].data_ptr()
+        a.n_small = plan.arrays[0]
+        for name, arr in zip(_SMALL, plan.arrays[1:]):
+            setattr(a, name, _ct.cast(arr, _vp) if arr is not None else None)
+    a.lr, a.beta1, a.beta2, a.eps, a.table_step = plan()
+
+
+def _call(entry, a, marching):
+    """The one call -> whether the next marches rode in its own launches, on this stream (no event to wait for then)."""
+    lib = L.lib()
+    before = lib.enerf_debug_carry_count(-2) if marching else 0
+    L.check(getattr(lib, "enerf_" + entry)(_ct.byref(a)), entry)
+    return bool(marching) and lib.enerf_debug_carry_count(-2) != before
+
+
+def _count_launches(points):
+    """The launch counters bench.py reads: the library issued one grid_encode_forward / backward over `points` rows."""
+    from .backends import _gridencoder as _gbk
+    _gbk.STATS["fwd_points"] += points
+    _gbk.STATS["budget_rows"] += points
+    _gbk.STATS["fwd_calls"] += 1
+    _gbk.STATS["bwd_points"] += points
+    _gbk.STATS["bwd_calls"] += 1
+    _gbk.LIFETIME["fwd_points"] += points
+    _gbk.LIFETIME["fwd_calls"] += 1
+
+
+def _hand_over(model, stash, staged, side_stream, carried):
+    """The stages just marched go into the stash, with the event their consumer waits for -> that event (None: carried)."""
+    ready = None
+    if not carried:
+        ready = torch.cuda.Event()
+        ready.record(side_stream)
+    for key, nxt in staged:
+        nxt["ready"] = ready
+        stash[key] = nxt
+    model._last_march_event = None if carried else (ready, side_stream)
+    return ready
+
+
+def _install_grads(ctx):
+    """p.grad of the MLP weights: views of the context's flat gradient buffer."""
+    views = ctx.get("grad_views")
+    if views is None:
+        views = ctx["grad_views"] = [g.view_as(p) for p, g in zip(ctx["weights"], ctx["grads"])]
+    for p, g in zip(ctx["weights"], views):
+        if p.grad is not g:
+            p.grad = g
+
+
+def train_step_native(model, rays_o, rays_d, target, opt, next_rays=None, side_stream=None, loss_out=None, perturb=True,
+                      dt_gamma=0, max_steps=1024, raw=False, defer_dp=False):
+    """One closed-form RGB step (loss = mean((image - target)^2), white background) through enerf_train_step_mse:
+    render of this batch (marched ahead of time when the previous step asked for it) + backward + the optimizer, and the
+    march of `next_rays` = (rays_o, rays_d) on `side_stream` behind the MLP backward.  -> blended image [N,3] (a buffer
+    that the next step of the same shape overwrites).  Gradients of the MLP weights are left in p.grad (views of one flat
+    buffer, likewise reused), the table's dense gradient buffer comes back clean; the optimizer's step counts advance.
+    raw=True (data parallel): the table's gradient is summed into the dense buffer `embeddings.grad` and NO optimizer
+    runs -- -> (image, flat MLP dW buffer); the caller averages both over the ranks and steps the optimizer."""
+    rays_o = rays_o.contiguous().view(-1, 3)
+    rays_d = rays_d.contiguous().view(-1, 3)
+    N, dev = rays_o.shape[0], rays_o.device
+    with torch.no_grad():
+        pre = _take_or_march(model, rays_o, rays_d, perturb, dt_gamma, max_steps, defer_cold_check=True)
+        stash = no = nd = nxt_counter = nxt_slot = None
+        cold_next = False
+        Nn = Mn = 0
+        if next_rays is not None and side_stream is not None:
+            stash = _stash_if_free(model)
+        if stash is not None:
+            no, nd = next_rays[0].contiguous().view(-1, 3), next_rays[1].contiguous().view(-1, 3)
+            Nn = no.shape[0]
+            mc = _budget(model)
+            cold_next = mc <= 0
+            if cold_next:                    # cold window: rows reserved from the last render whose count is known
+                Mn = model._cold_cap = cold_capacity(int(model._cold_rows), Nn, int(max_steps),
+                                                     int(getattr(model, "_cold_cap", 0)))
+            else:
+                Mn = mc + (128 - mc % 128)
+            nxt_counter = _next_counter(model)
+            nxt_slot = getattr(model, "last_counter_slot", None)
+
+        def prepare(pre):
+            ctx = _native_ctx(model, N, pre["M"], Nn, Mn, dev)
+            a = ctx["a"]
+            _fill_step(ctx, a)
+            _fill_samples(a, pre)
+            a.target = target.contiguous().view(-1, 3).data_ptr()
+            a.loss = None if loss_out is None else loss_out.data_ptr()
+            # (bit 1: the sharded tail with an owner range set -- this rank's slice of the table stays as record lists)
+            a.flags = (3 if defer_dp else 1) if raw else 0
+            nxt, which = None, 0
+            if stash is not None:
+                # (bit 4: this march stays on the side stream -- the cold window reads its count back behind it there)
+                _fill_march(a, model, side_stream, perturb, dt_gamma, max_steps, 16 if cold_next else 0)
+                nxt, which = _next_stage(a, ctx["stages"], ctx["flip"], pre, nxt_counter, nxt_slot, no, nd)
+            return ctx, a, nxt, which
+
+        ctx, a, nxt, which = prepare(pre)
+        if "cold_check" in pre:
+            # everything above was host work that did not need the count; only now is it waited for
+            fixed = _check_cold_stage(model, pre, rays_o, rays_d, perturb, dt_gamma, max_steps)
+            if fixed is not pre:
+                pre = fixed
+                ctx, a, nxt, which = prepare(pre)
+        M = pre["M"]
+        if nxt is not None:
+            ctx["flip"] = which ^ 1
+        if raw:
+            a.n_small = 0
+            ctx["plan"] = None                  # (a later optimizer-carrying step rebuilds its arrays)
+        else:
+            _fill_optimizer(ctx, a, opt)
+        cold_host = None
+        if nxt is not None and cold_next:
+            # the count of the cold window's next march travels to pinned memory (one slot per stage set): stored by the
+            # march itself (enerf_march_mirror_count) or copied behind it; what _check_cold_stage watches for is both words >= 0
+            hosts = ctx.get("cold_hosts")
+            if hosts is None:
+                hosts = ctx["cold_hosts"] = [torch.empty(2, dtype=torch.int32, pin_memory=True) for _ in range(2)]
+            cold_host = hosts[which]
+            cold_host.fill_(-1)
+            mirrored = MIRROR_COUNT
+            if mirrored:
+                L.check(L.lib().enerf_march_mirror_count(cold_host.data_ptr()), "march_mirror_count")
+        carried = _call("train_step_mse", a, nxt is not None)
+        _count_launches(M)
+        if nxt is not None:
+            if cold_next and not mirrored:
+                with torch.cuda.stream(side_stream):
+                    cold_host.copy_(nxt["counter"], non_blocking=True)
+            ready = _hand_over(model, stash, [(_stage_key(no, nd, perturb, dt_gamma, max_steps), nxt)], side_stream, carried)
+            if cold_next:
+                nxt["cold_check"] = (ready, cold_host, Mn)
+        if not raw:
+            _install_grads(ctx)
+    return (ctx["out_image"], ctx["dw"]) if raw else ctx["out_image"]
 
 
 def train_step_events_native(model, data, loss_opt, opt, next_data=None, side_stream=None, bg_color=None, perturb=True,
@@ -998,52 +983,33 @@ def train_step_events_native(model, data, loss_opt, opt, next_data=None, side_st
     `side_stream`.  -> (loss, delta).  Gradients of the MLP weights are left in p.grad, the table's dense gradient buffer
     comes back clean, the optimizer's step counts advance.  Values: those of events.train_step_events_manual +
     FusedAdam.step_grid_table (the same library calls, in the same order)."""
-    pairs = ((data["rays_evs_o1"], data["rays_evs_d1"]), (data["rays_evs_o2"], data["rays_evs_d2"]))
-    dev = pairs[0][0].device
+    flat = lambda d: [(d["rays_evs_o" + k].contiguous().view(-1, 3), d["rays_evs_d" + k].contiguous().view(-1, 3)) for k in "12"]
+    pairs = flat(data)
+    N, dev = pairs[0][0].shape[0], pairs[0][0].device
     with torch.no_grad():
         bg = torch.rand((1, 1, 3), device=dev) if bg_color is None else bg_color.detach().to(torch.float32).contiguous()
         pres, slots = [], []
         for ro, rd in pairs:
-            ro, rd = ro.contiguous().view(-1, 3), rd.contiguous().view(-1, 3)
-            pre = _take_premarched(model, ro, rd, perturb, dt_gamma, max_steps)
-            if pre is not None:
-                model.rendered_counter_slot = pre["slot"]
-            else:
-                counter = _next_counter(model)
-                model.rendered_counter_slot = getattr(model, "last_counter_slot", None)
-                pre = march_stage(model, ro, rd, counter, _budget(model), bool(perturb), False, float(dt_gamma),
-                                  int(max_steps))
-            pres.append(pre)
+            pres.append(_take_or_march(model, ro, rd, perturb, dt_gamma, max_steps))
             slots.append(model.rendered_counter_slot)
-        N = pairs[0][0].numel() // 3
-        nxt_pairs = None
+        stash = _stash_if_free(model) if next_data is not None and side_stream is not None else None
         Nn = Mn = 0
-        stash = getattr(model, "_premarched", None)
-        if not isinstance(stash, dict):
-            stash = model._premarched = {}
-        if next_data is not None and side_stream is not None and not any("pending" in p for p in stash.values()):
-            nxt_pairs = [(next_data["rays_evs_o1"].contiguous().view(-1, 3), next_data["rays_evs_d1"].contiguous().view(-1, 3)),
-                         (next_data["rays_evs_o2"].contiguous().view(-1, 3), next_data["rays_evs_d2"].contiguous().view(-1, 3))]
+        if stash is not None:
+            nxt_pairs = flat(next_data)
             Nn = nxt_pairs[0][0].shape[0]
             mc = _budget(model)
             Mn = mc + (128 - mc % 128)
         ctx = _native_events_ctx(model, N, (pres[0]["M"], pres[1]["M"]), Nn, Mn, bool(loss_opt.use_luma), dev)
-        a, emb, weights, grads = ctx["a"], ctx["emb"], ctx["weights"], ctx["grads"]
-        if emb.grad is None:
-            emb.grad = torch.zeros_like(emb)
+        a = ctx["a"]
+        _fill_step(ctx, a)
         loss = torch.empty((), dtype=torch.float32, device=dev)
-        a.stream = L.stream_handle()
         a.bg_color = bg.data_ptr()
         a.pols = data["pols"].contiguous().data_ptr()
         a.use_luma, a.linlog = int(bool(loss_opt.use_luma)), int(bool(loss_opt.linlog))
         a.C_thres, a.log_thres, a.upstream = float(loss_opt.C_thres), float(loss_opt.log_thres), 1.0
         a.loss = loss.data_ptr()
         for q, pre in enumerate(pres):
-            r = a.r[q]
-            r.xyzs, r.dirs, r.deltas = pre["xyzs"].data_ptr(), pre["dirs"].data_ptr(), pre["deltas"].data_ptr()
-            r.rays = pre["rays"].data_ptr()
-            r.counter = pre["counter"].data_ptr() if SKIP_PADDING_ROWS else None
-            r.next_rays_o = None
+            _fill_samples(a.r[q], pre)
         # merged layout: the second render's samples lie right behind the first's M rows (stages of one generation do)
         M0 = pres[0]["M"]
         merged = (ctx["tm"] is not None and pres[1]["M"] == M0
@@ -1052,63 +1018,21 @@ def train_step_events_native(model, data, loss_opt, opt, next_data=None, side_st
                   and pres[1]["deltas"].data_ptr() == pres[0]["deltas"].data_ptr() + 8 * M0)
         a.flags = 2 if merged else 0
         staged = []
-        if nxt_pairs is not None:
-            a.side_stream = side_stream.cuda_stream
-            a.dt_gamma, a.max_steps, a.perturb = float(dt_gamma), int(max_steps), 1 if perturb else 0
-            a.march_flags = occupied_box_flag(model) | 3 | 8
+        if stash is not None:
+            _fill_march(a, model, side_stream, perturb, dt_gamma, max_steps)
             for q, (no, nd) in enumerate(nxt_pairs):
-                st_bufs = ctx["stages"][q][ctx["flip"][q]]
-                if any(pres[q][k] is st_bufs[k] for k in ("xyzs", "rays")):
-                    st_bufs = ctx["stages"][q][ctx["flip"][q] ^ 1]
-                else:
-                    ctx["flip"][q] ^= 1
-                nxt = _Stage(st_bufs)
-                nxt["counter"] = _next_counter(model)
-                nxt["slot"] = getattr(model, "last_counter_slot", None)
-                r = a.r[q]
-                r.next_rays_o, r.next_rays_d, r.next_N, r.next_M = no.data_ptr(), nd.data_ptr(), Nn, Mn
-                for name in ("nears", "fars", "xyzs", "dirs", "deltas", "rays", "counter"):
-                    setattr(r, "next_" + name, nxt[name].data_ptr())
-                staged.append(((no.data_ptr(), nd.data_ptr(), Nn, bool(perturb), float(dt_gamma), int(max_steps)), nxt))
-        a.table_grad = emb.grad.data_ptr()
-        plan = ctx.get("plan")
-        if plan is None or ctx.get("plan_opt") is not opt:
-            plan = ctx["plan"] = opt.grid_table_plan(emb, list(weights), list(grads))
-            ctx["plan_opt"] = opt
-            small, st = plan.arrays, plan.state
-            a.table_m, a.table_v = st["exp_avg"].data_ptr(), st["exp_avg_sq"].data_ptr()
-            a.n_small = small[0]
-            for name, arr in zip(("small_p", "small_g", "small_m", "small_v", "small_n", "small_lr", "small_step"), small[1:]):
-                setattr(a, name, _ct.cast(arr, _vp) if arr is not None else None)
-        a.lr, a.beta1, a.beta2, a.eps, a.table_step = plan()
-        carried_before = L.lib().enerf_debug_carry_count(-2) if staged else 0
-        L.check(L.lib().enerf_train_step_events(_ct.byref(a)), "train_step_events")
-        # (the next step's marches may have ridden in this call's own launches, on this stream: no event to wait for then)
-        march_carried = bool(staged) and L.lib().enerf_debug_carry_count(-2) != carried_before
-        from .backends import _gridencoder as _gbk
-        # (the launch counters bench.py reads: merged, the library issued ONE grid_encode_forward / backward over 2 M points)
+                counter = _next_counter(model)
+                nxt, which = _next_stage(a.r[q], ctx["stages"][q], ctx["flip"][q], pres[q], counter,
+                                         getattr(model, "last_counter_slot", None), no, nd)
+                ctx["flip"][q] = which ^ 1
+                staged.append((_stage_key(no, nd, perturb, dt_gamma, max_steps), nxt))
+        _fill_optimizer(ctx, a, opt)
+        carried = _call("train_step_events", a, staged)
+        # (merged, the library issued ONE grid_encode_forward / backward over 2 M points)
         for points in ([pres[0]["M"] + pres[1]["M"]] if merged else [pre["M"] for pre in pres]):
-            _gbk.STATS["fwd_points"] += points
-            _gbk.STATS["budget_rows"] += points
-            _gbk.STATS["fwd_calls"] += 1
-            _gbk.STATS["bwd_points"] += points
-            _gbk.STATS["bwd_calls"] += 1
-            _gbk.LIFETIME["fwd_points"] += points
-            _gbk.LIFETIME["fwd_calls"] += 1
+            _count_launches(points)
         if staged:
-            ready = None
-            if not march_carried:
-                ready = torch.cuda.Event()
-                ready.record(side_stream)
-            for key, nxt in staged:
-                nxt["ready"] = ready
-                stash[key] = nxt
-            model._last_march_event = None if march_carried else (ready, side_stream)
-        views = ctx.get("grad_views")
-        if views is None:
-            views = ctx["grad_views"] = [g.view_as(p) for p, g in zip(weights, grads)]
-        for p, g in zip(weights, views):
-            if p.grad is not g:
-                p.grad = g
+            _hand_over(model, stash, staged, side_stream, carried)
+        _install_grads(ctx)
         model.rendered_counter_slot = slots[-1]
     return loss, ctx["delta"]

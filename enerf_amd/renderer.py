@@ -49,7 +49,7 @@ class NeRFRenderer(nn.Module):
     # one-call steps, samples marched ahead, events): none of it is model state.  torch.save(model) / copy.deepcopy(model)
     # see the module without it; the copy rebuilds what it needs on first use.
     _TRANSIENT = ("_density_scratch", "_native_ctx", "_native_events_ctx", "_premarched", "_fused_kind",
-                  "_pending_density_stats", "_last_march_event")
+                  "_pending_density_stats", "_last_march_event", "_ring_copy", "_ring_host", "_cold_watch_failed")
 
     def __getstate__(self):
         state = self.__dict__.copy()

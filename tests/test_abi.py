@@ -29,6 +29,52 @@ def test_header_symbols_exported_and_bound():
     assert _lib.lib().enerf_abi_version() == _lib.header_abi_version() >= 2
 
 
+def test_one_call_step_structs_match_the_header_layout(tmp_path):
+    """fused_render's ctypes mirrors of enerf_train_step_args / enerf_event_step_args (built from shared field lists) have
+    the header's sizeof and, field for field, its offsetof -- asked of a C compiler, not restated here."""
+    import shutil
+    import subprocess
+    from enerf_amd import fused_render as fr
+    cc = next((c for c in ("cc", "gcc", "clang", "g++", "hipcc") if shutil.which(c)), None)
+    assert cc is not None, "no C compiler on PATH"
+    cases = (("enerf_train_step_args", fr._StepArgs), ("enerf_event_step_args", fr._EventStepArgs))
+
+    def paths(struct, prefix=""):
+        for name, ctype in struct._fields_:
+            if isinstance(ctype, type) and issubclass(ctype, ctypes.Array):
+                for k in range(ctype._length_):
+                    yield from paths(ctype._type_, f"{prefix}{name}[{k}].")
+            else:
+                yield prefix + name
+
+    def offset(struct, path):
+        off = 0
+        for part in path.split("."):
+            m = re.fullmatch(r"(\w+)\[(\d+)\]", part)
+            field = getattr(struct, m.group(1) if m else part)
+            off += field.offset
+            if m:
+                struct = dict(struct._fields_)[m.group(1)]._type_
+                off += int(m.group(2)) * ctypes.sizeof(struct)
+        return off
+    lines = ["#include <stdio.h>", "#include \"enerf_hip.h\"", "int main(void) {"]
+    for cname, struct in cases:
+        lines.append(f'    printf("{cname} %zu\\n", sizeof({cname}));')
+        lines += [f'    printf("{cname}.{p} %zu\\n", offsetof({cname}, {p}));' for p in paths(struct)]
+    lines += ["    return 0;", "}"]
+    src = tmp_path / "layout.c"
+    src.write_text("\n".join(lines) + "\n")
+    exe = tmp_path / "layout"
+    subprocess.run([cc, "-I", os.path.join(ROOT, "include"), str(src), "-o", str(exe)], check=True)
+    want = dict(line.split() for line in subprocess.run([str(exe)], check=True, capture_output=True, text=True).stdout.splitlines())
+    for cname, struct in cases:
+        assert ctypes.sizeof(struct) == int(want[cname])
+        fields = list(paths(struct))
+        assert len(fields) >= 68
+        for p in fields:
+            assert offset(struct, p) == int(want[f"{cname}.{p}"]), (cname, p)
+
+
 def test_backends_expose_reference_function_names():
     from enerf_amd.backends import _raymarching, _gridencoder, _shencoder, _ffmlp
     # raymarching/src/bindings.cpp:5-20, gridencoder/src/bindings.cpp:5-8, shencoder/src/bindings.cpp:5-8,

@@ -1170,3 +1170,72 @@ def test_event_marches_carried_by_the_optimizer_launch_equal_the_side_stream_mar
     assert float(((la - lb).abs() / lb.abs().clamp(min=1e-9)).max()) <= 1e-5
     for n, a in pa.items():
         assert float((a - pb[n]).abs().mean()) <= 1e-4 * float(pb[n].abs().mean()) + 1e-9, n
+
+
+def test_model_with_a_staged_ring_copy_deep_copies_and_saves():
+    """What the fused routes cache on the module is not model state (renderer._TRANSIENT): with stage_ring_copy's event and
+    pinned buffer staged on it -- the window's last step, marches riding on the training stream -- the model still deep-copies
+    and pickles, and the copy holds none of it."""
+    import copy
+    import io
+    from enerf_amd.network import NeRFNetwork
+    from enerf_amd.trainer import TrainHarness
+    data = _batches(4, 4096, 2)
+    torch.manual_seed(0)
+    model = NeRFNetwork(encoding="hashgrid", bound=2, cuda_ray=True, out_dim_color=3).to(DEV)
+    h = TrainHarness(model, lr=1e-2, occupancy="synthetic")
+    for i in range(48):
+        nxt = data[(i + 1) % 4]
+        h.step_rgb(*data[i % 4], next_rays=(nxt[0], nxt[1]))
+        if "_ring_copy" in model.__dict__:
+            break
+    assert "_ring_copy" in model.__dict__ and "_ring_host" in model.__dict__ and "_native_ctx" in model.__dict__
+    twin = copy.deepcopy(model)
+    torch.save(model, io.BytesIO())
+    assert not any(k in twin.__dict__ for k in model._TRANSIENT)
+    assert not any(k in model.__getstate__() for k in model._TRANSIENT)
+    for (n, p), (n2, p2) in zip(model.named_parameters(), twin.named_parameters()):
+        assert n == n2 and torch.equal(p, p2)
+
+
+def test_one_call_step_refused_in_the_middle_leaves_nothing_armed():
+    """enerf_train_step_mse arms one-shot requests in the library's other files (valid-row counts, the MLP precision, the
+    side stream's signal ...).  A step that is refused half-way -- here the next batch's march with max_steps = 0, which
+    enerf_march_rays_train_ex rejects by argument validation, after the forward and the MLP backward have been issued with the
+    step's rows armed -- must leave none of them behind: the Python-driven steps that follow on the same model see the same
+    samples and losses as on a model that never made the failing call."""
+    import ctypes
+    from enerf_amd import _lib as L
+    from enerf_amd.network import NeRFNetwork
+    from enerf_amd.trainer import TrainHarness
+    data = _batches(4, 4096, 2)
+    runs = []
+    for fail in (True, False):
+        torch.manual_seed(0)
+        model = NeRFNetwork(encoding="hashgrid", bound=2, cuda_ray=True, out_dim_color=3).to(DEV)
+        h = TrainHarness(model, lr=1e-2, occupancy="synthetic")
+        for i in range(20):
+            nxt = data[(i + 1) % 4]
+            h.step_rgb(*data[i % 4], next_rays=(nxt[0], nxt[1]))
+        if fail:
+            # the last call's arguments once more (its buffers are the context's, its batch is data[3]: all alive), with a
+            # next march the library refuses; nothing is launched for that march, so the stage already marched stays intact
+            a = model._native_ctx["a"]
+            assert a.next_rays_o and a.counter
+            a.loss, a.max_steps = None, 0
+            rc = L.lib().enerf_train_step_mse(ctypes.byref(a))
+            assert rc == -1 and b"max_steps=0" in L.lib().enerf_last_error()          # ENERF_E_BADARG
+            a.max_steps = 1024
+        h.native_step = False
+        losses, counters = [], []
+        for i in range(20, 26):
+            nxt = data[(i + 1) % 4]
+            losses.append(float(h.step_rgb(*data[i % 4], next_rays=(nxt[0], nxt[1]))))
+            counters.append(model.step_counter[model.rendered_counter_slot].cpu().clone())
+        torch.cuda.synchronize()
+        runs.append((np.array(losses), torch.stack(counters)))
+    (la, ca), (lb, cb) = runs
+    assert torch.equal(ca, cb)
+    # (two runs of the same steps agree to the order of the float atomics of the table's smallest levels: the bound the
+    #  tests above put on the same pair of routes)
+    assert np.abs(la - lb).max() <= 1e-5 * np.abs(lb).max(), (la, lb)
