@@ -86,21 +86,32 @@ struct SplitJob {
     uint32_t* out;
     uint32_t threads;
 };
-// gridencoder.hip: the next fp32 D = 3, C = 2 forward launch carries `job` (one-shot; nullptr disarms).  Returns whether a
-// job armed earlier was still waiting (= no launch took it).
-bool grid_fwd_carry(const SplitJob* job);
-// gridencoder.hip: while set (device_count != nullptr), enerf_grid_encode_forward / _backward(_ex) treat their B rows as a
-// budget of which only base + min(*device_count, cap) (cap == 0: *device_count), rounded up to 32, are real -- the
+// grid_valid_rows -- the rows of a budget that are real: with count != nullptr the grid encoder's forward / backward treat
+// their B rows as a budget of which only base + min(*count, cap) (cap == 0: *count), rounded up to 32, are real -- the
 // convention of enerf_mlp32_valid_rows(_ex), whose kernels sit between the two and skip the same rows.  Results for real
-// rows are unchanged; the rest is neither encoded nor binned.  Set and cleared by the whole-step entry points only.
-void grid_valid_rows(const int32_t* device_count, uint32_t base, uint32_t cap);
-// mlp32.hip: the job that builds the fragments enerf_nerf_mlp_forward / _backward would build for these weights, and the
-// promise that it runs before them on `s`: the calls that follow with flags bit 0 use the fragments as they are.
+// rows are unchanged; the rest is neither encoded nor binned.  count == nullptr (the extern "C" entry points): all B rows.
+struct ValidRows {
+    const int32_t* count;      // device-side
+    uint32_t base, cap;
+};
+// gridencoder.hip: enerf_grid_encode_forward with the rows that count and, optionally, a job for its launch to carry.  The
+// fp32 D = 3, C = 2 launch carries a job of at most kCarryBlocks * kPtsPerBlock threads; *carried says whether it did.
+int grid_encode_forward(const float* inputs, const void* embeddings, const int32_t* offsets, void* outputs, uint32_t B,
+                        uint32_t D, uint32_t C, uint32_t L, float S, uint32_t H, int calc_grad_inputs, void* dy_dx,
+                        uint32_t gridtype, int dtype, int out_layout, float in_add, float in_mul, enerf_stream_t stream,
+                        const ValidRows& grid_valid_rows, const SplitJob* job = nullptr, bool* carried = nullptr);
+// ... and enerf_grid_encode_backward_ex with the same rows
+int grid_encode_backward(const void* grad, const float* inputs, const int32_t* offsets, void* grad_embeddings, uint32_t B,
+                         uint32_t D, uint32_t C, uint32_t L, float S, uint32_t H, int calc_grad_inputs, const void* dy_dx,
+                         void* grad_inputs, uint32_t gridtype, int dtype, int grad_layout, float in_add, float in_mul,
+                         uint32_t flags, uint32_t reserve_B, enerf_stream_t stream, const ValidRows& grid_valid_rows);
+// mlp32.hip: the job that builds the fragments enerf_nerf_mlp_forward / _backward would build for these weights (a launch
+// on `s` in front of them carries it) ...
 int nerf_mlp_frag_job(const float* const* wseg_s, const float* const* wseg_c, uint32_t w0_cols_c, uint32_t out_c,
                       hipStream_t s, SplitJob* job);
-// ... and the promise withdrawn: no launch took the job (or the launch that should have failed), the book-keeping of
-// "fragments current for these weight pointers" is void and the next MLP call rebuilds them whatever its flags say.
-void nerf_mlp_frags_invalidate();
+// ... and, once a launch has carried it: the fragments are current for these weights, the calls that follow with flags
+// bit 0 use them as they are.  (Not called: nothing is recorded and the next MLP call builds them itself.)
+void nerf_mlp_frags_built(const SplitJob& job, uint32_t w0_cols_c, uint32_t out_c);
 // Per-workgroup partial sums that the table optimizer's launch reduces on the fly: value i (< n) = sum over b < parts of
 // partial[b * stride + i], the gradient of element map[i] & 0xffffff of that launch's small tensor map[i] >> 24
 // (0xffffffff: of nobody).  (The fused MLP backward's weight gradients: k_mlp32_reduce_w2 and its 5 us leave the chain.)
@@ -109,9 +120,6 @@ struct PartialSums {
     const uint32_t* map;
     uint32_t parts, stride, n;
 };
-// gridencoder.hip: the next enerf_grid_adam_from_records(_ex) call sums `job` for its small tensors' gradients (and
-// stores them where it would have read them) -- one-shot; nullptr disarms.  Returns whether a job was still waiting.
-bool grid_adam_partial_sums(const PartialSums* job);
 // mlp32.hip: the job for the enerf_nerf_mlp_backward call that follows on `s` with flags bit 1 (B rows, same gradient
 // segments); small_g / small_n: the optimizer call's small tensors.  0: `job` is set; 1: does not apply (the small tensors
 // are not exactly the five gradient matrices, or loss scaling is armed); < 0: error.
@@ -143,23 +151,47 @@ struct MarchCountJob {
     float* nf_fars;
     uint32_t blocks;
 };
-// gridencoder.hip: the next enerf_grid_adam_from_records(_ex) launch of the plain fp32 C = 2 form carries `job` in
-// job->blocks extra workgroups.  Up to TWO jobs may wait (the event step's two renders): each call with a job appends;
-// nullptr disarms.  Returns whether a job armed earlier was still waiting.
-bool tile_adam_carry_count(const MarchCountJob* job);
-// raymarching.hip: march_rays_train_ex(...) split around a carrying launch.  begin: 0 = *job is the call's count pass (the
-// workspace is prepared, the one-shot near / far request consumed) and the call's scan + write are remembered for
-// march_carry_end; 1 = this call cannot be served that way (another marcher, a count mirror armed, a kept counter ...):
-// nothing consumed, make the ordinary call; < 0 = error.  end: scan + write on `s` (behind the launch that carried the job).
-// Up to two marches may be pending (begun one after the other: the second uses a chunk log of its own, WS_MARCH2); end
-// finishes all of them in the order they were begun.  `share`: how many marches will ride in the launch (splits the workgroups).
+// gridencoder.hip: enerf_grid_adam_from_records_ex with what rides in its launch.  `sums` (n != 0) is summed for the small
+// tensors' gradients, and stored where the launch would have read them, by the plain form with C = 2 and five small
+// tensors; the `n_counts` (<= 2: the event step's two renders) jobs of `counts`, each with blocks != 0 and N != 0, are
+// carried in their blocks extra workgroups by the plain C = 2 form.  The owner-range and loss-scaling forms take neither.
+// *taken: which of the two the launch took.
+enum { ADAM_TOOK_SUMS = 1u, ADAM_TOOK_COUNTS = 2u };
+int grid_adam_from_records(float* p, float* g, float* m, float* v, const int32_t* offsets, uint32_t L, uint32_t C, float lr,
+                           float beta1, float beta2, float eps, uint32_t step, uint32_t n_small, float* const* sp,
+                           const float* const* sg, float* const* sm, float* const* sv, const uint32_t* sn, const float* slr,
+                           const uint32_t* sstep, enerf_stream_t stream, const PartialSums* sums, const MarchCountJob* counts,
+                           uint32_t n_counts, uint32_t* taken);
+// raymarching.hip: what is left of a march whose count pass another launch carries -- its scan + write (march_carry_end)
+struct CarriedMarch {
+    const float *rays_o, *rays_d, *nears, *fars;
+    const uint8_t* grid;
+    float bound;
+    uint32_t max_steps, N, C, H, M, perturb, zero_unwritten;
+    float *xyzs, *dirs, *deltas;
+    int32_t *rays, *counter;
+    const void* log;             // ChunkEntry[N][kLogCap]
+    const uint32_t* nlog;
+};
+// raymarching.hip: march_rays_train_ex(...) split around a carrying launch, near / far computed inside the count pass from
+// nf_aabb / nf_min_near (enerf_march_fuse_near_far's arguments).  begin: 0 = *job is the call's count pass (the workspace
+// is prepared) and *march its scan + write; 1 = this call cannot be served that way (another marcher, a count mirror armed,
+// a kept counter ...): make the ordinary call; < 0 = error.  end: scan + write of the n marches on `s` (behind the launch
+// that carried the jobs), in order.  Two marches may be pending at a time, each with a chunk log of its own: `ws_slot` is
+// WS_MARCH or WS_MARCH2.  `share`: how many marches will ride in the launch (splits the workgroups).
 int march_carry_begin(const float* rays_o, const float* rays_d, const uint8_t* grid, float bound, float dt_gamma,
                       uint32_t max_steps, uint32_t N, uint32_t C, uint32_t H, uint32_t M, const float* nears,
                       const float* fars, float* xyzs, float* dirs, float* deltas, int32_t* rays, int32_t* counter,
-                      uint32_t perturb, uint32_t flags, hipStream_t s, MarchCountJob* job, uint32_t share = 1);
-int march_carry_end(hipStream_t s);
+                      uint32_t perturb, uint32_t flags, const float* nf_aabb, float nf_min_near, hipStream_t s, int ws_slot,
+                      MarchCountJob* job, CarriedMarch* march, uint32_t share = 1);
+int march_carry_end(const CarriedMarch* marches, uint32_t n, hipStream_t s);
 int march_carry_count_now(const MarchCountJob* job, hipStream_t s);     // (the carrying launch did not take the job)
-void march_carry_abort();                                               // (a step failed between begin and end)
+// raymarching.hip: enerf_march_rays_train_ex with the near / far request as arguments (a count mirror armed is still taken)
+int march_rays_train(const float* rays_o, const float* rays_d, const uint8_t* grid, float bound, float dt_gamma,
+                     uint32_t max_steps, uint32_t N, uint32_t C, uint32_t H, uint32_t M, const float* nears,
+                     const float* fars, float* xyzs, float* dirs, float* deltas, int32_t* rays, int32_t* counter,
+                     uint32_t perturb, uint32_t zero_unwritten, const float* nf_aabb, float nf_min_near,
+                     enerf_stream_t stream);
 
 // ---- wave-level primitives (wave64) ----------------------------------------
 __device__ __forceinline__ int lane_id() { return (int)(threadIdx.x & 63); }

@@ -64,7 +64,7 @@ struct LevelTab {
     float in_add, in_mul;  // inputs are read as (x + in_add) * in_mul: (0, 1) = as given; (bound, 1/(2 bound)) folds
                            // the wrapper's normalisation (grid.py:150) into the kernels, rounded exactly as torch's
                            // two elementwise kernels round it
-    // enerf::grid_valid_rows (the training step): the batch is a budget of B rows of which the marcher filled
+    // common.h grid_valid_rows (the training step): the batch is a budget of B rows of which the marcher filled
     // base + min(*valid_rows, cap) (cap == 0: *valid_rows) -- enerf_mlp32_valid_rows' convention, the MLP kernels between
     // this file's forward and backward skip the same rows.  Rows from that count rounded up to the MLP kernels' 32-row
     // tile onwards are neither encoded (nobody reads their features) nor binned (their gradient is zero).
@@ -460,7 +460,7 @@ __device__ __forceinline__ void split_job_block(const float* s0, const float* s1
     dst[64] = make_uint4(lo[0], lo[1], lo[2], lo[3]);
 }
 // (carry_blocks: the launch's first workgroups -- a multiple of 8, so that the forward's own keep their XCDs -- do `job`
-//  instead, enerf::grid_fwd_carry; 0 everywhere but in the training step's fp32 D = 3, C = 2 launch)
+//  instead, enerf::grid_encode_forward; 0 everywhere but in the training step's fp32 D = 3, C = 2 launch)
 constexpr uint32_t kCarryBlocks = 16;
 template <typename T, int D, int C>
 __global__ void __launch_bounds__(kPtsPerBlock) k_grid_fwd(const float* __restrict__ inputs, const T* __restrict__ grid,
@@ -1752,37 +1752,28 @@ int fill_level_tab(LevelTab& tab, uint32_t L, float S, uint32_t H, float in_add,
     return 0;
 }
 
-// enerf::grid_valid_rows (common.h): set by the whole-step entry points around their forward .. backward
-static const int32_t* g_grid_valid_rows = nullptr;
-static uint32_t g_grid_valid_base = 0, g_grid_valid_cap = 0;
-static inline void apply_valid_rows(LevelTab& tab) {
-    tab.valid_rows = g_grid_valid_rows;
-    tab.valid_base = g_grid_valid_base;
-    tab.valid_cap = g_grid_valid_cap;
+static inline void set_valid_rows(LevelTab& tab, const ValidRows& rows) {      // (common.h grid_valid_rows)
+    tab.valid_rows = rows.count;
+    tab.valid_base = rows.count ? rows.base : 0u;
+    tab.valid_cap = rows.count ? rows.cap : 0u;
 }
 
 __global__ void k_prof_mark() {}
 
-static SplitJob g_carry;              // enerf::grid_fwd_carry
-static bool g_carry_armed = false;
-static PartialSums g_partial_sums;     // enerf::grid_adam_partial_sums
-static bool g_partial_armed = false;
-static MarchCountJob g_count_job[2];    // enerf::tile_adam_carry_count
-static uint32_t g_count_armed = 0;      // jobs waiting
-
 template <typename T, int D>
 int launch_fwd(const float* inputs, const T* emb, const int32_t* offsets, T* outputs, uint32_t B, uint32_t C, uint32_t L,
                const LevelTab& tab, bool calc, T* dy_dx, uint32_t gridtype, int layout, hipStream_t s,
-               hipEvent_t ev_start, hipEvent_t ev_stop, const SweepGen& gen = SweepGen{}) {
+               hipEvent_t ev_start, hipEvent_t ev_stop, const SweepGen& gen = SweepGen{}, const SplitJob* ride = nullptr,
+               bool* carried = nullptr) {
     const uint32_t nchunks = div_up(layout == 2 ? ((B + 31u) & ~31u) : B, kPtsPerBlock);
     const uint32_t nblocks = fwd_blocks(nchunks, L);
     SplitJob job{};
     uint32_t carry = 0;
-    if (std::is_same<T, float>::value && D == 3 && C == 2 && g_carry_armed) {      // enerf::grid_fwd_carry: a job rides along
-        g_carry_armed = false;
-        job = g_carry;
+    if (std::is_same<T, float>::value && D == 3 && C == 2 && ride && ride->threads <= kCarryBlocks * kPtsPerBlock) {
+        job = *ride;                       // (common.h SplitJob: a job rides along)
         carry = kCarryBlocks;
     }
+    if (carried) *carried = carry != 0;
 #define ENERF_GF(CC)                                                                                               \
     do {                                                                                                           \
         if (ev_start) {                                                                                            \
@@ -2034,37 +2025,6 @@ int launch_bwd(const T* grad, const float* inputs, const int32_t* offsets, T* gr
 
 }  // namespace
 
-bool enerf::grid_adam_partial_sums(const PartialSums* job) {
-    const bool waiting = g_partial_armed;
-    g_partial_armed = job != nullptr && job->n != 0;
-    if (g_partial_armed) g_partial_sums = *job;
-    return waiting;
-}
-
-void enerf::grid_valid_rows(const int32_t* device_count, uint32_t base, uint32_t cap) {
-    g_grid_valid_rows = device_count;
-    g_grid_valid_base = device_count ? base : 0u;
-    g_grid_valid_cap = device_count ? cap : 0u;
-}
-
-bool enerf::tile_adam_carry_count(const MarchCountJob* job) {
-    const bool waiting = g_count_armed != 0;
-    if (job == nullptr || job->blocks == 0 || job->N == 0) {
-        g_count_armed = 0;
-        return waiting;
-    }
-    if (g_count_armed >= 2u) g_count_armed = 0;      // (never more than two: a third starts over)
-    g_count_job[g_count_armed++] = *job;
-    return waiting;
-}
-
-bool enerf::grid_fwd_carry(const SplitJob* job) {
-    const bool waiting = g_carry_armed;
-    g_carry_armed = job != nullptr && job->threads <= kCarryBlocks * kPtsPerBlock;
-    if (g_carry_armed) g_carry = *job;
-    return waiting;
-}
-
 extern "C" {
 
 // profiling aid, not part of the reference surface: restrict both grid kernels to the levels set in `mask`
@@ -2110,19 +2070,30 @@ int enerf_grid_encode_forward(const float* inputs, const void* embeddings, const
                               uint32_t B, uint32_t D, uint32_t C, uint32_t L, float S, uint32_t H, int calc_grad_inputs,
                               void* dy_dx, uint32_t gridtype, int dtype, int out_layout, float in_add, float in_mul,
                               enerf_stream_t stream) {
+    return enerf::grid_encode_forward(inputs, embeddings, offsets, outputs, B, D, C, L, S, H, calc_grad_inputs, dy_dx, gridtype,
+                                      dtype, out_layout, in_add, in_mul, stream, ValidRows{nullptr, 0, 0});
+}
+
+}  // extern "C"
+
+int enerf::grid_encode_forward(const float* inputs, const void* embeddings, const int32_t* offsets, void* outputs, uint32_t B,
+                               uint32_t D, uint32_t C, uint32_t L, float S, uint32_t H, int calc_grad_inputs, void* dy_dx,
+                               uint32_t gridtype, int dtype, int out_layout, float in_add, float in_mul, enerf_stream_t stream,
+                               const ValidRows& grid_valid_rows, const SplitJob* job, bool* carried) {
+    if (carried) *carried = false;
     if (B == 0) return 0;
     LevelTab tab;
     if (fill_level_tab(tab, L, S, H, in_add, in_mul)) ENERF_BADARG("GridEncoding: L must be in [1, %d], got %u", kMaxLevels, L);
     if (dtype != ENERF_F32 && dtype != ENERF_F16) ENERF_BADARG("GridEncoding: dtype must be f32 or f16");
     if (out_layout < 0 || out_layout > 2) ENERF_BADARG("GridEncoding: out_layout must be 0, 1 or 2, got %d", out_layout);
-    apply_valid_rows(tab);
+    set_valid_rows(tab, grid_valid_rows);
     hipStream_t s = (hipStream_t)stream;
     ProfScope prof(ENERF_K_GRID_FWD, s, true);   // timed with the kernel's own begin / end stamps
     prof.units((double)B);
     int rc = 0;
     const bool calc = calc_grad_inputs != 0;
     if (dtype == ENERF_F32) {
-        if (D == 3) rc = launch_fwd<float, 3>(inputs, (const float*)embeddings, offsets, (float*)outputs, B, C, L, tab, calc, (float*)dy_dx, gridtype, out_layout, s, prof.start(), prof.stop());
+        if (D == 3) rc = launch_fwd<float, 3>(inputs, (const float*)embeddings, offsets, (float*)outputs, B, C, L, tab, calc, (float*)dy_dx, gridtype, out_layout, s, prof.start(), prof.stop(), SweepGen{}, job, carried);
         else if (D == 2) rc = launch_fwd<float, 2>(inputs, (const float*)embeddings, offsets, (float*)outputs, B, C, L, tab, calc, (float*)dy_dx, gridtype, out_layout, s, prof.start(), prof.stop());
         else ENERF_BADARG("GridEncoding: D must be 2 or 3.");
     } else {
@@ -2134,6 +2105,8 @@ int enerf_grid_encode_forward(const float* inputs, const void* embeddings, const
     ENERF_LAUNCH_CHECK("grid_encode_forward");
     return 0;
 }
+
+extern "C" {
 
 int enerf_grid_encode_forward_sweep(const void* embeddings, const int32_t* offsets, void* outputs, uint32_t n_cascades,
                                     uint32_t grid_size, float bound, uint64_t seed, uint32_t C, uint32_t L, float S,
@@ -2172,12 +2145,24 @@ int enerf_grid_encode_backward_ex(const void* grad, const float* inputs, const v
                                   int grad_layout, float in_add, float in_mul, uint32_t flags, uint32_t reserve_B,
                                   enerf_stream_t stream) {
     (void)embeddings;
+    return enerf::grid_encode_backward(grad, inputs, offsets, grad_embeddings, B, D, C, L, S, H, calc_grad_inputs, dy_dx,
+                                       grad_inputs, gridtype, dtype, grad_layout, in_add, in_mul, flags, reserve_B, stream,
+                                       ValidRows{nullptr, 0, 0});
+}
+
+}  // extern "C"
+
+int enerf::grid_encode_backward(const void* grad, const float* inputs, const int32_t* offsets, void* grad_embeddings,
+                                uint32_t B, uint32_t D, uint32_t C, uint32_t L, float S, uint32_t H, int calc_grad_inputs,
+                                const void* dy_dx, void* grad_inputs, uint32_t gridtype, int dtype, int grad_layout,
+                                float in_add, float in_mul, uint32_t flags, uint32_t reserve_B, enerf_stream_t stream,
+                                const ValidRows& grid_valid_rows) {
     if (B == 0) return 0;
     LevelTab tab;
     if (fill_level_tab(tab, L, S, H, in_add, in_mul)) ENERF_BADARG("GridEncoding: L must be in [1, %d], got %u", kMaxLevels, L);
     if (dtype != ENERF_F32 && dtype != ENERF_F16) ENERF_BADARG("GridEncoding: dtype must be f32 or f16");
     if (grad_layout < 0 || grad_layout > 2) ENERF_BADARG("GridEncoding: grad_layout must be 0, 1 or 2, got %d", grad_layout);
-    apply_valid_rows(tab);
+    set_valid_rows(tab, grid_valid_rows);
     hipStream_t s = (hipStream_t)stream;
     ProfScope prof(ENERF_K_GRID_BWD, s);
     prof.units((double)B);
@@ -2196,6 +2181,8 @@ int enerf_grid_encode_backward_ex(const void* grad, const float* inputs, const v
     ENERF_LAUNCH_CHECK("grid_encode_backward");
     return 0;
 }
+
+extern "C" {
 
 int enerf_grid_encode_backward(const void* grad, const float* inputs, const void* embeddings, const int32_t* offsets,
                                void* grad_embeddings, uint32_t B, uint32_t D, uint32_t C, uint32_t L, float S, uint32_t H,
@@ -2239,6 +2226,21 @@ int enerf_grid_adam_from_records_ex(float* p, float* g, float* m, float* v, cons
                                     float lr, float beta1, float beta2, float eps, uint32_t step, uint32_t n_small,
                                     float* const* sp, const float* const* sg, float* const* sm, float* const* sv,
                                     const uint32_t* sn, const float* slr, const uint32_t* sstep, enerf_stream_t stream) {
+    return enerf::grid_adam_from_records(p, g, m, v, offsets, L, C, lr, beta1, beta2, eps, step, n_small, sp, sg, sm, sv, sn,
+                                         slr, sstep, stream, nullptr, nullptr, 0, nullptr);
+}
+
+}  // extern "C"
+
+int enerf::grid_adam_from_records(float* p, float* g, float* m, float* v, const int32_t* offsets, uint32_t L, uint32_t C,
+                                  float lr, float beta1, float beta2, float eps, uint32_t step, uint32_t n_small,
+                                  float* const* sp, const float* const* sg, float* const* sm, float* const* sv,
+                                  const uint32_t* sn, const float* slr, const uint32_t* sstep, enerf_stream_t stream,
+                                  const PartialSums* sums, const MarchCountJob* counts, uint32_t n_counts, uint32_t* taken) {
+    if (taken) *taken = 0;
+    if (n_counts > 2u) ENERF_BADARG("grid_adam_from_records: at most two count jobs ride in the launch");
+    for (uint32_t q = 0; q < n_counts; q++)
+        if (counts[q].blocks == 0 || counts[q].N == 0) ENERF_BADARG("grid_adam_from_records: count job %u is empty", q);
     if (n_small > (uint32_t)kMaxSmallAdam) ENERF_BADARG("grid_adam_from_records: at most %d extra tensors", kMaxSmallAdam);
     SmallAdam small;
     small.count = n_small;
@@ -2296,16 +2298,17 @@ int enerf_grid_adam_from_records_ex(float* p, float* g, float* m, float* v, cons
         return 0;
     }
     PartialSums ps{nullptr, nullptr, 0, 0, 0};
-    if (g_partial_armed && C == 2 && n_small == 5) {      // enerf::grid_adam_partial_sums: the small gradients are summed here
-        g_partial_armed = false;
-        ps = g_partial_sums;
+    uint32_t took = 0;
+    if (sums && sums->n != 0 && C == 2 && n_small == 5) {      // (common.h PartialSums: the small gradients are summed here)
+        ps = *sums;
+        took |= ADAM_TOOK_SUMS;
     }
     switch (C) {
         case 1: k_grid_tile_adam<1><<<kTilesPerCu * num_cus(), kTileThreads, kTileAccBytes, s>>>(offsets, p, g, m, v, L, min_tiles, recs, cursors, region, overflow, other, ad, small); break;
         case 2:
-            if (g_count_armed) {                     // enerf::tile_adam_carry_count: the next batch's march count pass(es) ride along
-                const MarchCountJob j0 = g_count_job[0], j1 = g_count_armed > 1u ? g_count_job[1] : MarchCountJob{};
-                g_count_armed = 0;
+            if (n_counts) {                          // (common.h MarchCountJob: the next batch's march count pass(es) ride along)
+                const MarchCountJob j0 = counts[0], j1 = n_counts > 1u ? counts[1] : MarchCountJob{};
+                took |= ADAM_TOOK_COUNTS;
                 k_grid_tile_adam<2, false, false, true><<<kTilesPerCu * num_cus() + j0.blocks + j1.blocks, kTileThreads, kTileAccBytes, s>>>(
                     offsets, p, g, m, v, L, min_tiles, recs, cursors, region, overflow, other, ad, small, AmpAdam{},
                     OwnerRange{0, 0, 1.0f}, ps, j0, j1);
@@ -2320,7 +2323,6 @@ int enerf_grid_adam_from_records_ex(float* p, float* g, float* m, float* v, cons
     if (g_pending.region != 0) g_session++;           // the next session counts overflows in the counter just cleared
     g_pending = PendingRecords();
     ENERF_LAUNCH_CHECK("grid_adam_from_records");
+    if (taken) *taken = took;
     return 0;
 }
-
-}  // extern "C"

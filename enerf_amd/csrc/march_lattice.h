@@ -1,7 +1,7 @@
 // march_lattice.h -- the device side of the fixed-step ("lattice") training marcher that more than one translation unit needs:
 // ray set-up, the occupancy-cell evaluation, the wave-per-ray lattice march with its chunk log, the replay, the occupied-box
 // clip, and the count pass as a workgroup-level function.  raymarching.hip builds its kernels from it; gridencoder.hip lets
-// k_grid_tile_adam's launch carry the NEXT batch's count pass in extra workgroups (enerf::tile_adam_carry_count, common.h), so
+// k_grid_tile_adam's launch carry the NEXT batch's count pass in extra workgroups (enerf::grid_adam_from_records, common.h), so
 // that in the one-call training step the march needs no second stream: the optimizer's launch counts, one small launch behind
 // it scans and writes.  Include INSIDE the translation unit's anonymous namespace, after common.h.
 // (reference: raymarching/src/raymarching.cu:320-478 march_rays_train; line citations at the functions)

@@ -1533,22 +1533,20 @@ int enerf::nerf_mlp_frag_job(const float* const* wseg_s, const float* const* wse
         g_nerf_map_gen = workspace_generation();
     }
     const float* w[5] = {wseg_s[0], wseg_s[3], wseg_c[0], wseg_c[1], wseg_c[3]};
-    for (int k = 0; k < 5; k++) {
-        job->src[k] = w[k];
-        g_nerf_built[k] = w[k];
-    }
-    g_nerf_built_cols = w0_cols_c;
-    g_nerf_built_out = out_c;
-    g_nerf_built_gen = workspace_generation();
+    for (int k = 0; k < 5; k++) job->src[k] = w[k];
     job->map = map;
     job->out = frags;
     job->threads = kNerfFragBytes / 2048 * 64;
     return 0;
 }
 
-void enerf::nerf_mlp_frags_invalidate() {
-    for (int k = 0; k < 5; k++) g_nerf_built[k] = nullptr;
-    g_nerf_built_gen = 0;
+// common.h: ... and a launch has carried it (what nerf_frags records behind its own build; a carrying launch takes no
+// workspace, so the generation is still the job's)
+void enerf::nerf_mlp_frags_built(const SplitJob& job, uint32_t w0_cols_c, uint32_t out_c) {
+    for (int k = 0; k < 5; k++) g_nerf_built[k] = job.src[k];
+    g_nerf_built_cols = w0_cols_c;
+    g_nerf_built_out = out_c;
+    g_nerf_built_gen = workspace_generation();
 }
 
 namespace enerf_mlp32 {

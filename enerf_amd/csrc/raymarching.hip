@@ -1265,7 +1265,7 @@ static int32_t* g_count_mirror = nullptr;      // enerf_march_mirror_count (arme
 // Both are one-shot requests for "the next march".  Every public march entry point takes them -- consumes AND disarms --
 // as its first statement, before any early return (N == 0, bad arguments, a workspace failure), so that a request can never
 // outlive the call it was made for and reach an unrelated march with a stale aabb / host pointer.  The whole-step entry
-// points disarm again on their way out (train_step.hip `done:`) in case they failed between arming and marching.
+// points disarm again on their way out (train_step.hip: ~Step) in case a request was armed for a march they never reached.
 struct MarchOneShot {
     const float* nf_aabb;
     float nf_min_near;
@@ -1405,7 +1405,19 @@ int enerf_march_rays_train_ex(const float* rays_o, const float* rays_d, const ui
                               const float* nears, const float* fars, float* xyzs, float* dirs, float* deltas,
                               int32_t* rays, int32_t* counter, uint32_t perturb, uint32_t zero_unwritten,
                               enerf_stream_t stream) {
-    const MarchOneShot once = march_take_oneshot();
+    // (the near / far request as arguments; the callee takes -- disarms -- both one-shots)
+    return enerf::march_rays_train(rays_o, rays_d, grid, bound, dt_gamma, max_steps, N, C, H, M, nears, fars, xyzs, dirs, deltas,
+                                   rays, counter, perturb, zero_unwritten, g_nf_aabb, g_nf_min_near, stream);
+}
+
+}  // extern "C"
+
+int enerf::march_rays_train(const float* rays_o, const float* rays_d, const uint8_t* grid, float bound, float dt_gamma,
+                            uint32_t max_steps, uint32_t N, uint32_t C, uint32_t H, uint32_t M, const float* nears,
+                            const float* fars, float* xyzs, float* dirs, float* deltas, int32_t* rays, int32_t* counter,
+                            uint32_t perturb, uint32_t zero_unwritten, const float* nf_aabb, float nf_min_near,
+                            enerf_stream_t stream) {
+    const MarchOneShot once = {nf_aabb, nf_min_near, march_take_oneshot().mirror};
     if (N == 0) {
         if (zero_unwritten && M) {
             (void)hipMemsetAsync(xyzs, 0, (size_t)M * 12, (hipStream_t)stream);
@@ -1427,6 +1439,8 @@ int enerf_march_rays_train_ex(const float* rays_o, const float* rays_d, const ui
     ENERF_LAUNCH_CHECK("march_rays_train");
     return 0;
 }
+
+extern "C" {
 
 int enerf_march_rays_train_count(const float* rays_o, const float* rays_d, const uint8_t* grid, float bound,
                                  float dt_gamma, uint32_t max_steps, uint32_t N, uint32_t C, uint32_t H,
@@ -1717,21 +1731,6 @@ int enerf_compact_rays(uint32_t n_alive, int32_t* rays_alive, const int32_t* ray
 }  // extern "C"
 
 // ---- the count pass carried by another launch (common.h: MarchCountJob) ------------------------------------------------------
-namespace {
-struct CarriedMarch {
-    bool pending = false;
-    const float *rays_o = nullptr, *rays_d = nullptr, *nears = nullptr, *fars = nullptr;
-    const uint8_t* grid = nullptr;
-    float bound = 0.0f;
-    uint32_t max_steps = 0, N = 0, C = 0, H = 0, M = 0, perturb = 0, zero_unwritten = 0;
-    float *xyzs = nullptr, *dirs = nullptr, *deltas = nullptr;
-    int32_t *rays = nullptr, *counter = nullptr;
-    const ChunkEntry* log = nullptr;
-    const uint32_t* nlog = nullptr;
-};
-CarriedMarch g_carried[2];
-uint32_t g_carried_n = 0;
-}  // namespace
 // workgroups of the carrying launch that count (enerf_debug_march_carry_blocks; 0 = two per compute unit)
 static uint32_t g_march_carry_blocks = getenv("ENERF_MARCH_CARRY_BLOCKS") ? (uint32_t)atoi(getenv("ENERF_MARCH_CARRY_BLOCKS")) : 0u;
 extern "C" int enerf_debug_march_carry_blocks(uint32_t blocks) {
@@ -1742,17 +1741,19 @@ extern "C" int enerf_debug_march_carry_blocks(uint32_t blocks) {
 int enerf::march_carry_begin(const float* rays_o, const float* rays_d, const uint8_t* grid, float bound, float dt_gamma,
                              uint32_t max_steps, uint32_t N, uint32_t C, uint32_t H, uint32_t M, const float* nears,
                              const float* fars, float* xyzs, float* dirs, float* deltas, int32_t* rays, int32_t* counter,
-                             uint32_t perturb, uint32_t flags, hipStream_t s, MarchCountJob* job, uint32_t share) {
+                             uint32_t perturb, uint32_t flags, const float* nf_aabb, float nf_min_near, hipStream_t s,
+                             int ws_slot, MarchCountJob* job, CarriedMarch* march, uint32_t share) {
     // what the carried form serves: the wave-per-ray lattice marcher, one-launch scan sizes, a counter taken as (0, 0)
     // (flags bit 3), no count mirror waiting (the cold window's host watches for k_march_scan's store)
     if (N == 0 || N > 16384u || C == 0 || H < 2 || max_steps == 0 || !(flags & 8u) || g_count_mirror != nullptr ||
-        g_carried_n >= 2u || !march_uses_lattice(dt_gamma, max_steps, C, H) || march_uses_threads(N, H))
+        !march_uses_lattice(dt_gamma, max_steps, C, H) || march_uses_threads(N, H))
         return 1;
-    const MarchOneShot once = march_take_oneshot();
+    if (ws_slot != WS_MARCH && ws_slot != WS_MARCH2) ENERF_BADARG("march_carry_begin: the chunk log is WS_MARCH or WS_MARCH2");
+    const MarchOneShot once = {nf_aabb, nf_min_near, nullptr};
     MarchCountJob j{};
     // (a second pending march logs into a workspace of its own: the first's log waits for its write pass)
     const int rc = march_train_count(rays_o, rays_d, grid, bound, dt_gamma, max_steps, N, C, H, nears, fars, rays, counter,
-                                     perturb, true, (flags & 4u) != 0, true, once, s, &j, g_carried_n == 0 ? WS_MARCH : WS_MARCH2);
+                                     perturb, true, (flags & 4u) != 0, true, once, s, &j, ws_slot);
     if (rc) return rc;
     if (!j.log) {
         set_error("march_carry_begin: the count pass was not handed over");
@@ -1761,15 +1762,8 @@ int enerf::march_carry_begin(const float* rays_o, const float* rays_d, const uin
     const uint32_t want = (g_march_carry_blocks ? g_march_carry_blocks : 2u * num_cus()) / (share ? share : 1u);
     j.blocks = min(div_up(N, 4), want ? want : 1u);
     *job = j;
-    CarriedMarch& c = g_carried[g_carried_n++];
-    c = CarriedMarch();
-    c.pending = true;
-    c.rays_o = rays_o; c.rays_d = rays_d; c.grid = grid; c.bound = bound;
-    c.max_steps = max_steps; c.N = N; c.C = C; c.H = H; c.M = M;
-    c.nears = nears; c.fars = fars; c.xyzs = xyzs; c.dirs = dirs; c.deltas = deltas;
-    c.rays = rays; c.counter = counter; c.perturb = perturb; c.zero_unwritten = flags & 1u;
-    c.log = static_cast<const ChunkEntry*>(j.log);
-    c.nlog = j.nlog;
+    *march = {rays_o,  rays_d,     nears, fars, grid,   bound, max_steps, N,     C,     H, M,
+              perturb, flags & 1u, xyzs,  dirs, deltas, rays,  counter,   j.log, j.nlog};
     return 0;
 }
 
@@ -1780,24 +1774,17 @@ int enerf::march_carry_count_now(const MarchCountJob* job, hipStream_t s) {
     ENERF_LAUNCH_CHECK("march_rays_train (count, uncarried)");
     return 0;
 }
-// a step that failed between begin and end
-void enerf::march_carry_abort() { g_carried_n = 0; }
 
-int enerf::march_carry_end(hipStream_t s) {
-    if (g_carried_n == 0) {
-        set_error("march_carry_end: no carried march is pending");
-        return ENERF_E_BADARG;
-    }
-    const uint32_t n = g_carried_n;
-    g_carried_n = 0;
+int enerf::march_carry_end(const CarriedMarch* marches, uint32_t n, hipStream_t s) {
+    if (n == 0) ENERF_BADARG("march_carry_end: no carried march is pending");
     if (int e = workspace_family_enter(0, s)) return e;
     ProfScope prof(ENERF_K_MARCH_TRAIN, s);
     for (uint32_t k = 0; k < n; k++) {
-        const CarriedMarch m = g_carried[k];
+        const CarriedMarch& m = marches[k];
         const uint32_t ray_blocks = div_up(m.N, 4);
         k_march_scan_write_w<<<ray_blocks + (m.zero_unwritten ? 128u : 0u), 256, 0, s>>>(
             m.rays_o, m.rays_d, m.grid, m.bound, m.max_steps, m.N, m.C, m.H, m.M, m.nears, m.fars, m.xyzs, m.dirs, m.deltas,
-            m.rays, m.perturb, m.log, m.nlog, m.counter, m.zero_unwritten, ray_blocks);
+            m.rays, m.perturb, static_cast<const ChunkEntry*>(m.log), m.nlog, m.counter, m.zero_unwritten, ray_blocks);
     }
     ENERF_LAUNCH_CHECK("march_rays_train (carried)");
     return 0;

@@ -16,8 +16,9 @@
 //     optimizer():      table Adam from the records + the MLP weights' Adam (one launch)
 // The NEXT batch's march runs on the side stream behind the MLP backward, whose last launch carries the signal that stream
 // waits for (marches_side), or without a second stream: its count pass rides in the optimizer's launch, scan + write follow
-// it (marches_begin, optimizer).  Whatever a step arms in the other translation units is armed through its Step object,
-// which disarms on the way out.
+// it (marches_begin, optimizer).  What rides in another kernel's launch -- the fragments' build, the weight-gradient sums,
+// the count passes -- is an argument of that launch's internal entry point (common.h) and a local value here; only the public
+// one-shots that the Python-driven route uses as well are armed, through the Step object, which disarms on the way out.
 #include <hip/hip_runtime.h>
 
 #include <chrono>
@@ -48,14 +49,19 @@ extern "C" int enerf_debug_carry_count(int on) {
 
 namespace {
 
-// The one-shots of a step: process-global requests in gridencoder.hip / mlp32.hip / raymarching.hip that the next matching
-// library call consumes.  One method arms each and remembers it; the destructor disarms what is still armed, so a step that
-// returns early leaves nothing behind for the next, unrelated call.
+// The public one-shots of a step: process-global requests in mlp32.hip / raymarching.hip that the next matching library
+// call consumes.  One method arms each and remembers it; the destructor disarms what is still armed, so a step that returns
+// early leaves nothing behind for the next, unrelated call.  And what one function of the step hands a later one.
 class Step {
 public:
     bool fused;                            // both nets as one launch each way (csrc/nerf_mlp.hip: the split-bf16 default)
+    // for the optimizer's launch: the fused backward's weight-gradient partial sums (has_sums) ...
     PartialSums sums{nullptr, nullptr, 0, 0, 0};
-    MarchCountJob count_jobs[2] = {};      // the next marches riding in this step's optimizer launch (the first counts())
+    bool has_sums = false;
+    // ... and the next marches' count passes, with the scan + write that follow them (the first `counts`)
+    MarchCountJob count_jobs[2] = {};
+    CarriedMarch marches[2] = {};
+    uint32_t counts = 0;
 
     template <class A>
     Step(const A* a, bool timed) : timed_(timed) {
@@ -72,16 +78,6 @@ public:
         // (one-shot march requests never outlive the step they were armed for -- csrc/raymarching.hip: MarchOneShot)
         enerf_march_fuse_near_far(nullptr, 0.0f);
         enerf_march_mirror_count(nullptr);
-        grid_valid_rows(nullptr, 0, 0);
-        if (counts_) {                     // (failed between march_carry_begin and march_carry_end)
-            tile_adam_carry_count(nullptr);
-            march_carry_abort();
-        }
-        if (own_sums_) grid_adam_partial_sums(nullptr);
-        if (frags_) {                      // (the launch that should have carried the fragments' build never ran)
-            grid_fwd_carry(nullptr);
-            nerf_mlp_frags_invalidate();
-        }
         if (defer_) enerf_mlp32_defer_reduce(0);
         if (signal_) enerf_mlp32_signal_next_reduce(0);
         if (mlp_rows_) enerf_mlp32_valid_rows(nullptr);
@@ -101,19 +97,7 @@ public:
         return rc;
     }
 
-    void carry_frags(const SplitJob* job) {
-        grid_fwd_carry(job);
-        frags_ = true;
-    }
-    uint32_t frags_taken() {               // 1: the grid forward built the fragments, the MLP calls are told so
-        if (!frags_) return 0;
-        frags_ = false;
-        if (!grid_fwd_carry(nullptr)) return 1;
-        nerf_mlp_frags_invalidate();
-        return 0;
-    }
     // (the budget's unfilled rows are skipped: real rows = base + min(*counter, cap), cap == 0: *counter; nullptr: all)
-    void grid_rows(const int32_t* counter, uint32_t base, uint32_t cap) { grid_valid_rows(counter, base, cap); }
     void mlp_rows(const int32_t* counter, uint32_t base, uint32_t cap) {
         if (!counter) return;
         enerf_mlp32_valid_rows_ex(counter, base, cap);
@@ -131,33 +115,10 @@ public:
         enerf_mlp32_signal_next_reduce(on ? 1 : 0);
         signal_ = on;
     }
-    void own_sums(bool on) { own_sums_ = on; }       // `sums` is the job of the MLP backward that follows
-    bool has_sums() const { return own_sums_; }
-    void arm_sums() {
-        if (own_sums_) grid_adam_partial_sums(&sums);
-    }
-    bool sums_left() {                     // the optimizer's launch did not take them
-        const bool left = own_sums_ && grid_adam_partial_sums(nullptr);
-        own_sums_ = false;
-        return left;
-    }
-    uint32_t counts() const { return counts_; }
-    MarchCountJob* count_begin() { return &count_jobs[counts_]; }
-    void count_begun() { counts_++; }
-    void counts_drop() {                   // not this way after all: every march takes the side stream
-        march_carry_abort();
-        counts_ = 0;
-    }
-    void arm_counts() {
-        for (uint32_t q = 0; q < counts_; q++) tile_adam_carry_count(&count_jobs[q]);
-    }
-    bool counts_left() { return tile_adam_carry_count(nullptr); }
-    void counts_done() { counts_ = 0; }
 
 private:
     int prev_prec_ = -1;
-    bool frags_ = false, mlp_rows_ = false, defer_ = false, signal_ = false, own_sums_ = false;
-    uint32_t counts_ = 0;
+    bool mlp_rows_ = false, defer_ = false, signal_ = false;
     bool timed_;
     int slot_ = 0;
     std::chrono::steady_clock::time_point t_prev_;
@@ -199,16 +160,18 @@ template <class A>
 int forward(Step& st, const A* a, const Batch& b, bool carry, uint32_t frags) {
     enerf_stream_t s = a->stream;
     SplitJob job{};
-    if (st.fused && carry && g_carry_frags) {
+    const bool ride = st.fused && carry && g_carry_frags;
+    if (ride)
         if (int rc = st.run(nerf_mlp_frag_job(a->wseg_s, a->wseg_c, a->w0_cols_c, a->out_c, (hipStream_t)s, &job), 0)) return rc;
-        st.carry_frags(&job);
-    }
-    st.grid_rows(b.counter, b.base, b.cap);
-    if (int rc = st.run(enerf_grid_encode_forward(b.xyzs, a->embeddings, a->offsets, b.feats, b.rows, 3, 2, 16,
-                                                  a->level_scale_log2, a->base_resolution, 0, b.feats, a->gridtype, ENERF_F32,
-                                                  2, a->bound, a->inv_two_bound, s)))
+    bool carried = false;
+    if (int rc = st.run(grid_encode_forward(b.xyzs, a->embeddings, a->offsets, b.feats, b.rows, 3, 2, 16, a->level_scale_log2,
+                                            a->base_resolution, 0, b.feats, a->gridtype, ENERF_F32, 2, a->bound,
+                                            a->inv_two_bound, s, {b.counter, b.base, b.cap}, ride ? &job : nullptr, &carried)))
         return rc;
-    frags |= st.frags_taken();
+    if (carried) {                         // the grid forward built the fragments, the MLP calls are told so
+        nerf_mlp_frags_built(job, a->w0_cols_c, a->out_c);
+        frags = 1;
+    }
     st.mlp_rows(b.counter, b.base, b.cap);
     int rc;
     if (st.fused) {
@@ -236,11 +199,11 @@ int backward(Step& st, const A* a, const Batch& b, bool signal, bool fold) {
     int rc;
     if (st.fused) {
         if (fold && g_fold_reduce)
-            st.own_sums(nerf_mlp_partial_job(a->dwseg_s, a->dwseg_c, a->w0_cols_c, a->out_c, a->small_g, a->small_n, a->n_small,
-                                             b.rows, (hipStream_t)s, &st.sums) == 0);
+            st.has_sums = nerf_mlp_partial_job(a->dwseg_s, a->dwseg_c, a->w0_cols_c, a->out_c, a->small_g, a->small_n, a->n_small,
+                                               b.rows, (hipStream_t)s, &st.sums) == 0;
         rc = st.run(enerf_nerf_mlp_backward(b.g_rgbs, b.g_sigmas, 1.0f, b.feats, b.dirs, b.rgb, a->wseg_s, a->wseg_c, a->dwseg_s,
                                             a->dwseg_c, a->w0_cols_c, b.overwrite, b.rows, a->out_c, b.dfeat,
-                                            st.has_sums() ? 3u : 1u, s),
+                                            st.has_sums ? 3u : 1u, s),
                     2);
     } else {
         st.defer_reduce(true);             // (the colour net's partial sums wait for the sigma net's reduce launch)
@@ -257,25 +220,22 @@ int backward(Step& st, const A* a, const Batch& b, bool signal, bool fold) {
     return rc;
 }
 
-// The next marches carried by the optimizer's launch where that applies: all of them or none (st.counts()).  Decided in front
+// The next marches carried by the optimizer's launch where that applies: all of them or none (st.counts).  Decided in front
 // of the MLP backward, because the side-stream form needs its signal armed there.
 template <class A>
 int marches_begin(Step& st, const A* a, const NextMarch* next, uint32_t n, bool carry) {
     if (!carry || !g_carry_count || (a->march_flags & 16u)) return 0;
     for (uint32_t q = 0; q < n; q++) {
         const NextMarch& m = next[q];
-        enerf_march_fuse_near_far(a->aabb, a->min_near);           // (near / far inside the count pass)
+        // (near / far inside the count pass; the second pending march logs into a workspace of its own)
         const int b = march_carry_begin(m.rays_o, m.rays_d, a->bitfield, a->bound, a->dt_gamma, a->max_steps, m.N, a->cascade,
                                         a->grid_size, m.M, m.nears, m.fars, m.xyzs, m.dirs, m.deltas, m.rays, m.counter,
-                                        a->perturb, a->march_flags, (hipStream_t)a->stream, st.count_begin(), n);
+                                        a->perturb, a->march_flags, a->aabb, a->min_near, (hipStream_t)a->stream,
+                                        q == 0 ? WS_MARCH : WS_MARCH2, &st.count_jobs[q], &st.marches[q], n);
         if (b < 0) return b;
-        if (b != 0) {
-            enerf_march_fuse_near_far(nullptr, 0.0f);              // (nothing consumed: the ordinary call arms it again)
-            st.counts_drop();
-            return 0;
-        }
-        st.count_begun();
+        if (b != 0) return 0;              // not this way after all: every march takes the side stream
     }
+    st.counts = n;
     return 0;
 }
 
@@ -287,10 +247,9 @@ int marches_side(Step& st, const A* a, const NextMarch* next, uint32_t n) {
     for (uint32_t q = 0; q < n; q++) {
         const NextMarch& m = next[q];
         // (near / far inside the march's count pass: one launch less at the head of the chain the next step waits for)
-        if (int rc = st.run(enerf_march_fuse_near_far(a->aabb, a->min_near))) return rc;
-        if (int rc = st.run(enerf_march_rays_train_ex(m.rays_o, m.rays_d, a->bitfield, a->bound, a->dt_gamma, a->max_steps, m.N,
-                                                      a->cascade, a->grid_size, m.M, m.nears, m.fars, m.xyzs, m.dirs, m.deltas,
-                                                      m.rays, m.counter, a->perturb, a->march_flags, ss)))
+        if (int rc = st.run(march_rays_train(m.rays_o, m.rays_d, a->bitfield, a->bound, a->dt_gamma, a->max_steps, m.N,
+                                             a->cascade, a->grid_size, m.M, m.nears, m.fars, m.xyzs, m.dirs, m.deltas, m.rays,
+                                             m.counter, a->perturb, a->march_flags, a->aabb, a->min_near, ss)))
             return rc;
     }
     return 0;
@@ -299,11 +258,9 @@ int marches_side(Step& st, const A* a, const NextMarch* next, uint32_t n) {
 // defer 1: record lists for the optimizer pass (b.total rows reserved); 0: the backward's own flush into the dense buffer
 template <class A>
 int table_backward(Step& st, const A* a, const Batch& b, uint32_t defer) {
-    st.grid_rows(b.counter, b.base, b.cap);
-    return st.run(enerf_grid_encode_backward_ex(b.dfeat, b.xyzs, a->embeddings, a->offsets, a->table_grad, b.rows, 3, 2, 16,
-                                                a->level_scale_log2, a->base_resolution, 0, b.dfeat, b.dfeat, a->gridtype,
-                                                ENERF_F32, 2, a->bound, a->inv_two_bound, defer, defer ? b.total : 0u,
-                                                a->stream));
+    return st.run(grid_encode_backward(b.dfeat, b.xyzs, a->offsets, a->table_grad, b.rows, 3, 2, 16, a->level_scale_log2,
+                                       a->base_resolution, 0, b.dfeat, b.dfeat, a->gridtype, ENERF_F32, 2, a->bound,
+                                       a->inv_two_bound, defer, defer ? b.total : 0u, a->stream, {b.counter, b.base, b.cap}));
 }
 
 // Table Adam from the records + the MLP weights' Adam, with what the step hands the launch (weight-gradient sums, count
@@ -311,21 +268,20 @@ int table_backward(Step& st, const A* a, const Batch& b, uint32_t defer) {
 template <class A>
 int optimizer(Step& st, const A* a, const char* who) {
     enerf_stream_t s = a->stream;
-    st.arm_sums();
-    st.arm_counts();
-    if (int rc = st.run(enerf_grid_adam_from_records_ex(a->table, a->table_grad, a->table_m, a->table_v, a->offsets, 16, 2, a->lr,
-                                                        a->beta1, a->beta2, a->eps, a->table_step, a->n_small, a->small_p,
-                                                        a->small_g, a->small_m, a->small_v, a->small_n, a->small_lr,
-                                                        a->small_step, s)))
+    uint32_t taken = 0;
+    if (int rc = st.run(grid_adam_from_records(a->table, a->table_grad, a->table_m, a->table_v, a->offsets, 16, 2, a->lr, a->beta1,
+                                               a->beta2, a->eps, a->table_step, a->n_small, a->small_p, a->small_g, a->small_m,
+                                               a->small_v, a->small_n, a->small_lr, a->small_step, s,
+                                               st.has_sums ? &st.sums : nullptr, st.count_jobs, st.counts, &taken)))
         return rc;
-    if (st.sums_left()) ENERF_BADARG("%s: the optimizer launch did not take the weight gradients' partial sums", who);
-    if (!st.counts()) return 0;
-    // (an optimizer form that carries nothing -- loss scaling armed -- leaves the jobs waiting: counted by launches of their own)
-    if (st.counts_left())
-        for (uint32_t q = 0; q < st.counts(); q++)
+    if (st.has_sums && !(taken & ADAM_TOOK_SUMS))
+        ENERF_BADARG("%s: the optimizer launch did not take the weight gradients' partial sums", who);
+    if (!st.counts) return 0;
+    // (an optimizer form that carries nothing -- loss scaling armed -- did not take the jobs: counted by launches of their own)
+    if (!(taken & ADAM_TOOK_COUNTS))
+        for (uint32_t q = 0; q < st.counts; q++)
             if (int rc = st.run(march_carry_count_now(&st.count_jobs[q], (hipStream_t)s))) return rc;
-    if (int rc = st.run(march_carry_end((hipStream_t)s))) return rc;
-    st.counts_done();
+    if (int rc = st.run(march_carry_end(st.marches, st.counts, (hipStream_t)s))) return rc;
     g_carried_steps++;
     return 0;
 }
@@ -370,7 +326,7 @@ extern "C" int enerf_train_step_mse(const enerf_train_step_args* a) {
                                                                a->stream)))
         return rc;
     if (int rc = marches_begin(st, a, next, n_next, !dp)) return rc;
-    const bool side = n_next && !st.counts();
+    const bool side = n_next && !st.counts;
     if (int rc = backward(st, a, b, side, !dp)) return rc;
     if (side)
         if (int rc = marches_side(st, a, next, n_next)) return rc;
@@ -406,7 +362,7 @@ static int train_step_events_merged(const enerf_event_step_args* a) {
                                     b.g_rgbs + k * M * a->out_c))
             return rc;
     if (int rc = marches_begin(st, a, next, n_next, true)) return rc;
-    const bool side = n_next && !st.counts();
+    const bool side = n_next && !st.counts;
     if (int rc = backward(st, a, b, side, true)) return rc;
     if (side)
         if (int rc = marches_side(st, a, next, n_next)) return rc;

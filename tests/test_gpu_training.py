@@ -1172,6 +1172,44 @@ def test_event_marches_carried_by_the_optimizer_launch_equal_the_side_stream_mar
         assert float((a - pb[n]).abs().mean()) <= 1e-4 * float(pb[n].abs().mean()) + 1e-9, n
 
 
+@pytest.mark.parametrize("n_rays", [64, 4096])
+def test_count_jobs_the_optimizer_launch_did_not_take_are_counted_by_their_own_launch(n_rays):
+    """csrc/train_step.hip optimizer(): under loss scaling (enerf_amp_begin: TrainHarness(fp16=True), whose steady-state
+    steps are the one-call step) the table optimizer's launch is the form that carries nothing, so the next march's count
+    job, prepared for it, runs as a launch of its own (march_carry_count_now) in front of the scan + write.  The marched
+    batches are those of the side-stream march: samples depend on the rays and the fixed occupancy only, so the per-step
+    sample counters of 12 steps are equal bit for bit.  (The harness reaches the carried march by itself once a sample
+    budget exists: the 12 steps follow the cold window and its update_extra_state, 17 steps that are not compared.)"""
+    from enerf_amd import _lib
+    from enerf_amd.network import NeRFNetwork
+    from enerf_amd.trainer import TrainHarness
+    lib = _lib.lib()
+    data = _batches(4, n_rays, 2)
+    runs = {}
+    prev = lib.enerf_debug_carry_count(-1)
+    try:
+        for carried in (1, 0):
+            lib.enerf_debug_carry_count(carried)
+            torch.manual_seed(0)
+            model = NeRFNetwork(encoding="hashgrid", bound=2, cuda_ray=True, out_dim_color=3).to(DEV)
+            h = TrainHarness(model, lr=1e-2, occupancy="synthetic", fp16=True)
+            assert h.amp_f16
+            counters = []
+            for i in range(17 + 12):      # (the cold window and its update_extra_state, then 12 steady-state steps)
+                nxt = data[(i + 1) % 4]
+                h.step_rgb(*data[i % 4], next_rays=(nxt[0], nxt[1]))
+                counters.append(model.step_counter[model.rendered_counter_slot].clone())
+                if i == 16:
+                    taken0 = lib.enerf_debug_carry_count(-2)
+            torch.cuda.synchronize()
+            runs[carried] = (torch.stack(counters[17:]).cpu(), lib.enerf_debug_carry_count(-2) - taken0)
+    finally:
+        lib.enerf_debug_carry_count(prev)
+    (ca, na), (cb, nb) = runs[1], runs[0]
+    assert na > 0 and nb == 0, (na, nb)
+    assert int(ca.sum()) > 0 and torch.equal(ca, cb)
+
+
 def test_model_with_a_staged_ring_copy_deep_copies_and_saves():
     """What the fused routes cache on the module is not model state (renderer._TRANSIENT): with stage_ring_copy's event and
     pinned buffer staged on it -- the window's last step, marches riding on the training stream -- the model still deep-copies

@@ -58,7 +58,7 @@ if h.native_step:
     arr = (ctypes.c_double * 16)()
     _lib.lib().enerf_debug_step_timing(0, arr)
     names = ["grid_fwd", "mlp_fwd_sigma", "mlp_fwd_colour", "composite", "mlp_bwd_colour", "mlp_bwd_sigma(+reduce)",
-             "wait_signal", "near_far", "march", "grid_bwd", "table_adam"]
+             "wait_signal", "march", "grid_bwd", "table_adam"]
     print("host us per call inside enerf_train_step_mse:", {n: round(arr[k], 1) for k, n in enumerate(names)},
           "sum", round(sum(arr), 1))
 if _a.stub and h.native_step:
