@@ -105,6 +105,43 @@ int grid_encode_backward(const void* grad, const float* inputs, const int32_t* o
                          uint32_t D, uint32_t C, uint32_t L, float S, uint32_t H, int calc_grad_inputs, const void* dy_dx,
                          void* grad_inputs, uint32_t gridtype, int dtype, int grad_layout, float in_add, float in_mul,
                          uint32_t flags, uint32_t reserve_B, enerf_stream_t stream, const ValidRows& grid_valid_rows);
+// mlp32.hip: what an MLP call takes from its caller, where the public calls take the process's settings: the rows that
+// count (as above), the arithmetic mode (enerf_mlp32_precision's 0..3) and whether X / Y / dY / dX are 16-bit
+struct MlpCall {
+    ValidRows rows;
+    int mode;
+    bool io16;
+};
+// The weight-gradient partial sums of a backward that launched no reduce, for the backward that follows to reduce with its
+// own in one launch (the colour net's, then the sigma net's).  Not `filled` to begin with and after the reduce; `job` is
+// storage for mlp32.hip's own ReduceJob, which only that file reads.
+struct DeferredReduce {
+    bool filled;
+    uint64_t job[10];
+};
+// mlp32.hip: enerf_mlp32_forward_p / _backward_p, enerf_nerf_mlp_available / _forward / _backward with their modifiers as
+// arguments; no process setting is read or changed.  Backward, `signal`: the last launch carries the completion signal and
+// *signalled becomes the event that carried it (for hipStreamWaitEvent; left alone when no launch did; pass one wherever
+// `signal` is set: with a null `signalled` the launch still carries the signal, but nobody can wait on it).  `pair`, empty:
+// this call's sums are left in it and no reduce is launched; filled: the reduce launch takes both and empties it.
+int mlp32_forward_p(const float* X, const float* const* wseg, uint32_t w0_cols, uint32_t nerf_perm, uint32_t B,
+                    uint32_t in_dim, uint32_t out_dim, uint32_t num_hidden, uint32_t activation, uint32_t output_activation,
+                    float* fb, float* Y, uint32_t x_layout, uint32_t y_stride, float* y0_exp, const float* sh_dirs,
+                    enerf_stream_t stream, const MlpCall& c);
+int mlp32_backward_p(const float* dY, const float* X, const float* const* wseg, float* const* dwseg, uint32_t w0_cols,
+                     uint32_t nerf_perm, uint32_t overwrite, const float* fb, uint32_t B, uint32_t in_dim, uint32_t out_dim,
+                     uint32_t num_hidden, uint32_t activation, float* bb, float* dX, uint32_t x_layout, uint32_t dy_stride,
+                     const float* y_sigmoid, uint32_t y_sigmoid_stride, const float* dsigma, const float* h0,
+                     uint32_t h0_stride, enerf_stream_t stream, const MlpCall& c, bool signal, hipEvent_t* signalled,
+                     DeferredReduce* pair);
+bool nerf_mlp_available(int mode);
+int nerf_mlp_forward(const float* feats, const float* dirs, const float* const* wseg_s, const float* const* wseg_c,
+                     uint32_t w0_cols_c, uint32_t B, uint32_t out_c, float* sigma, float* rgb, uint32_t flags,
+                     enerf_stream_t stream, const MlpCall& c);
+int nerf_mlp_backward(const float* g_rgb, const float* g_sigma, float sigma_scale, const float* feats, const float* dirs,
+                      const float* rgb, const float* const* wseg_s, const float* const* wseg_c, float* const* dwseg_s,
+                      float* const* dwseg_c, uint32_t w0_cols_c, uint32_t overwrite, uint32_t B, uint32_t out_c, float* dfeat,
+                      uint32_t flags, enerf_stream_t stream, const MlpCall& c, bool signal, hipEvent_t* signalled);
 // mlp32.hip: the job that builds the fragments enerf_nerf_mlp_forward / _backward would build for these weights (a launch
 // on `s` in front of them carries it) ...
 int nerf_mlp_frag_job(const float* const* wseg_s, const float* const* wseg_c, uint32_t w0_cols_c, uint32_t out_c,

@@ -21,6 +21,7 @@
 // 256 contiguous bytes per level.
 #include <hip/hip_runtime.h>
 #include <cstdlib>
+#include <cstring>
 #include <hip/hip_ext.h>
 
 #include "common.h"
@@ -846,8 +847,9 @@ __global__ void __launch_bounds__(1024) k_mlp32_reduce_w2(ReduceJob a, ReduceJob
     else reduce_w_body(b.partial, b.nblocks, b.NW, b.dst, blockIdx.x - na, found_inf, b.stride);
 }
 
-static const int32_t* g_valid_rows = nullptr;      // enerf_mlp32_valid_rows
-static uint32_t g_valid_base = 0, g_valid_cap = 0;  // enerf_mlp32_valid_rows_ex
+// The process's requests for the PUBLIC calls (the valid rows, the signal, the deferral, and g_precision / g_io16_p below):
+// public_call() assembles one call's modifiers from them and nothing else reads them; the launching code takes arguments.
+static ValidRows g_valid = {nullptr, 0, 0};   // enerf_mlp32_valid_rows(_ex)
 static bool g_signal_armed = false;      // enerf_mlp32_signal_next_reduce
 static bool g_signal_recorded = false;
 static hipEvent_t g_signal_event = nullptr;
@@ -857,17 +859,25 @@ constexpr unsigned kSignalEventFlags = hipEventDisableTiming | hipEventReleaseTo
 #else
 constexpr unsigned kSignalEventFlags = hipEventDisableTiming;
 #endif
+// The completion signal of a backward: its last launch carries this event as its stop event -- a kernel-attached
+// completion signal costs the stream nothing, where an event record after the launch is a packet of its own that the next
+// kernel waits for (tools/launch_chain.hip: +0 against +3 us per kernel).  nullptr: the event could not be made.
+// (tried and dropped, tools/step_timeline.py: a device-scope release event -- same ~6 us before the next kernel of this
+// stream; a generation number published by the reduce launch's last workgroup + a sleeping wait kernel on the other
+// stream -- the gap goes, the reduce launch grows by 3 us, the step does not move)
+hipEvent_t signal_event() {
+    if (!g_signal_event && hipEventCreateWithFlags(&g_signal_event, kSignalEventFlags) != hipSuccess) g_signal_event = nullptr;
+    return g_signal_event;
+}
 static bool g_defer_next = false;        // one-shot: set by enerf_mlp32_defer_reduce
-static bool g_have_pending = false;
-static ReduceJob g_pending;
+static DeferredReduce g_pending = {};    // (filled: left behind by the backward that consumed the one-shot)
 
 bool g_fused_bwd = true;            // dgrad + wgrad in one kernel (num_hidden <= 2)
 int g_precision = 1;                // enerf_mlp32_precision: 0 = fp32 MFMA (bit-exact fmaf chains), 1 = split-bf16 (x3),
                                     // 2 = bf16 operands (the FFMLP nets' arithmetic: one product, 16-bit roundings),
                                     // 3 = fp16 operands (the same kernels on IEEE half: the reference's fp16 regime)
-inline bool ops16() { return g_precision == 2 || g_precision == 3; }
-bool g_io16 = false;                // ffmlp16_forward / _backward: X, Y, dY, dX are 16-bit row-major tensors
-bool g_io16_p = false;              // enerf_mlp32_io16: the same for the enerf_mlp32_*_p calls (fp16 operands only)
+inline bool ops16(int mode) { return mode == 2 || mode == 3; }
+bool g_io16_p = false;              // enerf_mlp32_io16: 16-bit X, Y, dY, dX for the enerf_mlp32_*_p calls (fp16 operands only)
 bool g_recompute = true;            // enerf_mlp32_recompute: the split backward recomputes the hidden activations
 // three hidden layers (the FFMLP colour net on 16-bit operands) recompute whatever the switch says: mlp32s.hip has no
 // activation-loading instance of that shape
@@ -879,9 +889,9 @@ uint32_t g_bwd_blocks = 0;          // 0: default cap of the fused backward grid
 
 // shapes the split / bf16 backward kernel serves: one or two hidden layers in either mode, three (the FFMLP colour net,
 // row-major input) with bf16 operands
-bool split_bwd_shape(uint32_t num_hidden, uint32_t out_dim, uint32_t x_layout) {
-    return g_fused_bwd && g_precision != 0 && out_dim <= 16 &&
-           (num_hidden <= 2 || (ops16() && num_hidden == 3 && x_layout == 0));
+bool split_bwd_shape(int mode, uint32_t num_hidden, uint32_t out_dim, uint32_t x_layout) {
+    return g_fused_bwd && mode != 0 && out_dim <= 16 &&
+           (num_hidden <= 2 || (ops16(mode) && num_hidden == 3 && x_layout == 0));
 }
 
 uint32_t pgrid(uint32_t B, uint32_t cap) {
@@ -894,16 +904,10 @@ uint32_t pgrid(uint32_t B, uint32_t cap) {
 extern "C" {
 
 // Applies to the mlp32 forward / backward calls that follow, until set again (NULL: every row is real).
-int enerf_mlp32_valid_rows(const int32_t* device_count) {
-    g_valid_rows = device_count;
-    g_valid_base = g_valid_cap = 0;
-    return 0;
-}
+int enerf_mlp32_valid_rows(const int32_t* device_count) { return enerf_mlp32_valid_rows_ex(device_count, 0, 0); }
 // real rows = base + min(*device_count, cap)  (cap == 0: as enerf_mlp32_valid_rows)
 int enerf_mlp32_valid_rows_ex(const int32_t* device_count, uint32_t base, uint32_t cap) {
-    g_valid_rows = device_count;
-    g_valid_base = device_count ? base : 0;
-    g_valid_cap = device_count ? cap : 0;
+    g_valid = {device_count, device_count ? base : 0, device_count ? cap : 0};
     return 0;
 }
 
@@ -954,23 +958,40 @@ int enerf_debug_mlp32_wgrad_blocks(uint32_t blocks) {
     return 0;
 }
 
+}  // extern "C"
+
 // Fused fp32 MLP: X -> (64 x num_hidden, ReLU/none) -> Y [B,out_dim], out_dim <= 32, no bias.  B is ragged; with
 // Bp = B rounded up to 32: X is [B,32] row-major (x_layout 0) or [16,Bp,2] level-major (x_layout 1);
 // weights: [W0 64x32 | Wh (num_hidden-1) x 64x64 | Wout out_dim x 64]; fb: num_hidden*Bp*64 floats of forward
 // activations in this file's own tile order (opaque to the caller; only enerf_mlp32_backward reads it) or NULL (inference).
 
-static WSrc blob_src(const float* W, uint32_t num_hidden) {
+// the caller's weight / gradient segments {first layer, hidden 0, hidden 1, output layer} (unused hidden slots dropped) ...
+static WSrc seg_src(const float* const* wseg, uint32_t num_hidden, uint32_t w0_cols, uint32_t nerf_perm, const ValidRows& rows) {
     WSrc w;
-    w.seg[0] = W;
-    w.seg[1] = num_hidden > 1 ? W + HID * IN : nullptr;
-    w.seg[2] = num_hidden > 2 ? W + HID * IN + HID * HID : nullptr;
-    w.seg[3] = W + HID * IN + (num_hidden - 1) * HID * HID;
-    w.w0_cols = IN;
-    w.nerf_perm = 0;
-    w.valid_rows = g_valid_rows;
-    w.valid_base = g_valid_base;
-    w.valid_cap = g_valid_cap;
+    for (uint32_t k = 0; k < 4; k++) w.seg[k] = (k == 0 || k == 3 || k < num_hidden) ? wseg[k] : nullptr;
+    w.w0_cols = w0_cols;
+    w.nerf_perm = nerf_perm;
+    w.valid_rows = rows.count;
+    w.valid_base = rows.base;
+    w.valid_cap = rows.cap;
     return w;
+}
+static WDst seg_dst(float* const* dwseg, uint32_t num_hidden, uint32_t w0_cols, uint32_t nerf_perm, uint32_t overwrite) {
+    WDst d;
+    for (uint32_t k = 0; k < 4; k++) d.seg[k] = (k == 0 || k == 3 || k < num_hidden) ? dwseg[k] : nullptr;
+    d.w0_cols = w0_cols;
+    d.nerf_perm = nerf_perm;
+    d.overwrite = overwrite;
+    return d;
+}
+// ... and those of a contiguous blob
+static WSrc blob_src(const float* W, uint32_t num_hidden, const ValidRows& rows) {
+    const float* seg[4] = {W, W + HID * IN, W + HID * IN + HID * HID, W + HID * IN + (num_hidden - 1) * HID * HID};
+    return seg_src(seg, num_hidden, IN, 0, rows);
+}
+static WDst blob_dst(float* dW, uint32_t num_hidden, uint32_t overwrite) {
+    float* seg[4] = {dW, dW + HID * IN, dW + HID * IN + HID * HID, dW + HID * IN + (num_hidden - 1) * HID * HID};
+    return seg_dst(seg, num_hidden, IN, 0, overwrite);
 }
 static int segs_ok(const void* const* seg, uint32_t num_hidden, uint32_t w0_cols, uint32_t nerf_perm, const char* what) {
     if (!seg || !seg[0] || !seg[3] || (num_hidden > 1 && !seg[1]) || (num_hidden > 2 && !seg[2])) {
@@ -987,9 +1008,9 @@ static int segs_ok(const void* const* seg, uint32_t num_hidden, uint32_t w0_cols
 static int mlp32_forward_impl(const float* X, WSrc W, uint32_t B, uint32_t in_dim, uint32_t out_dim,
                               uint32_t num_hidden, uint32_t activation, uint32_t output_activation, float* fb, float* Y,
                               uint32_t x_layout, uint32_t y_stride, float* y0_exp, const float* sh_dirs,
-                              enerf_stream_t stream) {
+                              enerf_stream_t stream, int mode, bool io16) {
     if (B == 0) return 0;
-    if (sh_dirs && !((num_hidden == 1 || (num_hidden == 2 && g_precision != 0)) && x_layout == 1 && Y && out_dim <= 16 &&
+    if (sh_dirs && !((num_hidden == 1 || (num_hidden == 2 && mode != 0)) && x_layout == 1 && Y && out_dim <= 16 &&
                      (y_stride == 0 ? out_dim : y_stride) >= 32))
         ENERF_BADARG("mlp32_forward_sh: needs one hidden layer (two in the bf16 modes), level-major input, out_dim <= 16 "
                      "and rows of >= 32 floats");
@@ -1005,14 +1026,14 @@ static int mlp32_forward_impl(const float* X, WSrc W, uint32_t B, uint32_t in_di
     if (int eg = single_device_guard("mlp32_forward")) return eg;
     hipStream_t s = (hipStream_t)stream;
     // (the split kernels are timed by their own begin / end stamps; the fp32 MFMA kernels between two event packets)
-    ProfScope prof(ENERF_K_FFMLP_FWD, s, g_precision != 0);
+    ProfScope prof(ENERF_K_FFMLP_FWD, s, mode != 0);
     prof.units((double)B);
     // two workgroups per CU are resident (the weights sit in ~130-210 registers): one round of them, each wave
     // setting up once, beats four short-lived ones per CU (measured at the 138 k-sample training batch)
     // (split operands: the weights sit in LDS as operands -- 2 KiB per fragment, hi + lo -- over the staged fp32 copy,
     // and three workgroups per CU are resident)
     const bool sigma_only_shape = num_hidden == 1 && !fb && !Y && y0_exp && x_layout == 1;
-    const bool lds_operands = g_precision == 1 && !sigma_only_shape;
+    const bool lds_operands = mode == 1 && !sigma_only_shape;
     const uint32_t grid = pgrid(B, g_fwd_blocks ? g_fwd_blocks : (lds_operands ? 768 : 512));
     size_t lds = sizeof(float) * (HID * IN + (num_hidden - 1) * HID * HID + out_dim * HID);
     if (lds_operands && lds < (size_t)(8 + 8 * (num_hidden - 1)) * 2048) lds = (size_t)(8 + 8 * (num_hidden - 1)) * 2048;
@@ -1029,12 +1050,12 @@ static int mlp32_forward_impl(const float* X, WSrc W, uint32_t B, uint32_t in_di
         }                                                     \
     } while (0)
     const bool sigma_only = num_hidden == 1 && !fb && !Y && y0_exp && x_layout == 1;
-    if (g_precision != 0) {
+    if (mode != 0) {
         // (a training forward whose backward recomputes the activations is the inference kernel)
-        const bool store_fb = fb != nullptr && !(recompute_for(num_hidden) && split_bwd_shape(num_hidden, out_dim, x_layout));
-        (g_precision == 3 ? mlp32s_f16_launch_fwd : mlp32s_launch_fwd)(
-            g_precision == 1 ? 3 : 1, num_hidden, store_fb, x_layout, sigma_only, X, W, fb, Y, B, out_dim, activation,
-            output_activation, y_stride, y0_exp, sh_dirs, grid, lds, s, prof.start(), prof.stop(), g_io16);
+        const bool store_fb = fb != nullptr && !(recompute_for(num_hidden) && split_bwd_shape(mode, num_hidden, out_dim, x_layout));
+        (mode == 3 ? mlp32s_f16_launch_fwd : mlp32s_launch_fwd)(
+            mode == 1 ? 3 : 1, num_hidden, store_fb, x_layout, sigma_only, X, W, fb, Y, B, out_dim, activation,
+            output_activation, y_stride, y0_exp, sh_dirs, grid, lds, s, prof.start(), prof.stop(), io16);
     } else if (sh_dirs) {
         const ShNorm4 nrm = make_sh_norm4();
         if (fb)
@@ -1055,61 +1076,33 @@ static int mlp32_forward_impl(const float* X, WSrc W, uint32_t B, uint32_t in_di
     return 0;
 }
 
-int enerf_mlp32_forward(const float* X, const float* W, uint32_t B, uint32_t in_dim, uint32_t out_dim,
-                        uint32_t num_hidden, uint32_t activation, uint32_t output_activation, float* fb, float* Y,
-                        uint32_t x_layout, uint32_t y_stride, float* y0_exp, enerf_stream_t stream) {
-    if (num_hidden < 1 || num_hidden > 3) ENERF_BADARG("mlp32: num_hidden must be 1..3, got %u", num_hidden);
-    return mlp32_forward_impl(X, blob_src(W, num_hidden), B, in_dim, out_dim, num_hidden, activation, output_activation,
-                              fb, Y, x_layout, y_stride, y0_exp, nullptr, stream);
-}
-
-int enerf_mlp32_forward_sh(const float* X, const float* W, uint32_t B, uint32_t in_dim, uint32_t out_dim,
-                           uint32_t num_hidden, uint32_t activation, uint32_t output_activation, float* fb, float* Y,
-                           uint32_t x_layout, uint32_t y_stride, float* y0_exp, const float* sh_dirs,
-                           enerf_stream_t stream) {
-    if (num_hidden < 1 || num_hidden > 3) ENERF_BADARG("mlp32: num_hidden must be 1..3, got %u", num_hidden);
-    return mlp32_forward_impl(X, blob_src(W, num_hidden), B, in_dim, out_dim, num_hidden, activation, output_activation,
-                              fb, Y, x_layout, y_stride, y0_exp, sh_dirs, stream);
-}
-
-// The same forward with the weights where the caller keeps them: wseg = {first layer, hidden 0, hidden 1, output layer}
-// (unused hidden slots NULL); w0_cols / nerf_perm as in WSrc above.
-int enerf_mlp32_forward_p(const float* X, const float* const* wseg, uint32_t w0_cols, uint32_t nerf_perm, uint32_t B,
-                          uint32_t in_dim, uint32_t out_dim, uint32_t num_hidden, uint32_t activation,
-                          uint32_t output_activation, float* fb, float* Y, uint32_t x_layout, uint32_t y_stride,
-                          float* y0_exp, const float* sh_dirs, enerf_stream_t stream) {
+// common.h: enerf_mlp32_forward_p with its modifiers.  wseg = {first layer, hidden 0, hidden 1, output layer} (unused
+// hidden slots NULL); w0_cols / nerf_perm as in WSrc.
+int enerf::mlp32_forward_p(const float* X, const float* const* wseg, uint32_t w0_cols, uint32_t nerf_perm, uint32_t B,
+                           uint32_t in_dim, uint32_t out_dim, uint32_t num_hidden, uint32_t activation,
+                           uint32_t output_activation, float* fb, float* Y, uint32_t x_layout, uint32_t y_stride,
+                           float* y0_exp, const float* sh_dirs, enerf_stream_t stream, const MlpCall& c) {
     if (num_hidden < 1 || num_hidden > 3) ENERF_BADARG("mlp32: num_hidden must be 1..3, got %u", num_hidden);
     if (int e = segs_ok((const void* const*)wseg, num_hidden, w0_cols, nerf_perm, "mlp32_forward_p")) return e;
-    WSrc w;
-    for (int k = 0; k < 4; k++) w.seg[k] = wseg[k];
-    if (num_hidden < 3) w.seg[2] = nullptr;
-    if (num_hidden < 2) w.seg[1] = nullptr;
-    w.w0_cols = w0_cols;
-    w.nerf_perm = nerf_perm;
-    w.valid_rows = g_valid_rows;
-    w.valid_base = g_valid_base;
-    w.valid_cap = g_valid_cap;
-    if (!g_io16_p)
-        return mlp32_forward_impl(X, w, B, in_dim, out_dim, num_hidden, activation, output_activation, fb, Y, x_layout,
-                                  y_stride, y0_exp, sh_dirs, stream);
-    if (g_precision != 3) ENERF_BADARG("mlp32_forward_p: 16-bit I/O (enerf_mlp32_io16) serves precision 3 only");
-    if (num_hidden < 2 || out_dim > 16 || x_layout != 0 || sh_dirs || y0_exp || !Y)
+    if (c.io16 && c.mode != 3) ENERF_BADARG("mlp32_forward_p: 16-bit I/O (enerf_mlp32_io16) serves precision 3 only");
+    if (c.io16 && (num_hidden < 2 || out_dim > 16 || x_layout != 0 || sh_dirs || y0_exp || !Y))
         ENERF_BADARG("mlp32_forward_p: 16-bit I/O needs two or three hidden layers, out_dim <= 16, row-major X, an output "
                      "Y and no SH / density epilogue");
-    g_io16 = true;
-    const int rc = mlp32_forward_impl(X, w, B, in_dim, out_dim, num_hidden, activation, output_activation, fb, Y, x_layout,
-                                      y_stride, y0_exp, sh_dirs, stream);
-    g_io16 = false;
-    return rc;
+    return mlp32_forward_impl(X, seg_src(wseg, num_hidden, w0_cols, nerf_perm, c.rows), B, in_dim, out_dim, num_hidden,
+                              activation, output_activation, fb, Y, x_layout, y_stride, y0_exp, sh_dirs, stream, c.mode, c.io16);
 }
 
 // dY [B,out_dim], fb from the forward; bb [num_hidden,Bp,64] scratch (written); dX NULL, [B,32] (x_layout 0) or
 // [16,Bp,2] (x_layout 1, pad rows written as zeros); dW (fp32 blob) is ACCUMULATED into (+=).
+// `signal`: the reduce launch carries the completion signal, *signalled is the event (left alone when no launch carried it).
+// `pair` (common.h DeferredReduce), empty: this call's partial sums wait in it, in their own workspace, and no reduce is
+// launched; filled: the reduce launch takes both calls' sums and empties it.
 static int mlp32_backward_impl(const float* dY, const float* X, WSrc W, const float* fb, uint32_t B, uint32_t in_dim,
                                uint32_t out_dim, uint32_t num_hidden, uint32_t activation, float* bb, float* dX,
                                WDst dW, uint32_t x_layout, uint32_t dy_stride, const float* y_sigmoid,
                                uint32_t y_sigmoid_stride, const float* dsigma, const float* h0, uint32_t h0_stride,
-                               enerf_stream_t stream) {
+                               enerf_stream_t stream, int mode, bool io16, bool signal, hipEvent_t* signalled,
+                               DeferredReduce* pair) {
     if (B == 0) return 0;
     if (in_dim != IN) ENERF_BADARG("mlp32: in_dim must be 32, got %u", in_dim);
     if (out_dim == 0 || out_dim > 32) ENERF_BADARG("mlp32: out_dim must be in [1, 32], got %u", out_dim);
@@ -1131,12 +1124,12 @@ static int mlp32_backward_impl(const float* dY, const float* X, WSrc W, const fl
     const size_t lds_w = sizeof(float) * (((NW + 3u) & ~3u) + (x_layout == 1 ? 4 * 16 * XT_LD : 0));
     // the split / bf16 kernels: one or two hidden layers in either mode, three (the FFMLP colour net, row-major input) with
     // bf16 operands
-    const bool split_bwd = split_bwd_shape(num_hidden, out_dim, x_layout);
+    const bool split_bwd = split_bwd_shape(mode, num_hidden, out_dim, x_layout);
     // timing (enerf_prof_*): the split kernel by its own begin / end stamps, the weight-gradient reduce launch as a family
     // of its own (ENERF_K_MLP_REDUCE); the fp32 MFMA route between two event packets around all of its launches
     ProfScope prof(ENERF_K_FFMLP_BWD, s, split_bwd);
     prof.units((double)B);
-    if (ops16() && !split_bwd)
+    if (ops16(mode) && !split_bwd)
         ENERF_BADARG("mlp32_backward: 16-bit operands (precision 2 / 3) need out_dim <= 16 and at most three hidden layers");
     const bool fused = split_bwd || (g_fused_bwd && num_hidden <= 2);
     if (!fused && W.valid_rows)
@@ -1148,10 +1141,7 @@ static int mlp32_backward_impl(const float* dY, const float* X, WSrc W, const fl
     // workspace for the weight-gradient kernel (whose inner loop is load-bound)
     const bool fused_dy = !fused && (y_sigmoid != nullptr || dsigma != nullptr || dys.stride != out_dim);
     const size_t part_bytes = sizeof(float) * (size_t)wgrid * NW;
-    // one-shot deferral (enerf_mlp32_defer_reduce): this call's partial sums wait, in their own workspace, for the next
-    // call's reduce launch
-    const bool defer = g_defer_next && !g_have_pending;
-    g_defer_next = false;
+    const bool defer = pair && !pair->filled;
     if (int ew = workspace_family_enter(1, s)) return ew;
     float* partial = (float*)workspace(defer ? WS_MLP32_DEFER : WS_FFMLP,
                                        part_bytes + (fused_dy ? sizeof(float) * (size_t)B * out_dim : 0));
@@ -1189,9 +1179,9 @@ static int mlp32_backward_impl(const float* dY, const float* X, WSrc W, const fl
     } while (0)
     if (split_bwd) {
         (void)bb;
-        (g_precision == 3 ? mlp32s_f16_launch_bwd : mlp32s_launch_bwd)(
-            g_precision == 1 ? 3 : 1, num_hidden, x_layout, dys, X, W, fb, dX, partial, B, out_dim, activation, wgrid, s,
-            prof.start(), prof.stop(), recompute_for(num_hidden) || g_io16, g_io16);
+        (mode == 3 ? mlp32s_f16_launch_bwd : mlp32s_launch_bwd)(
+            mode == 1 ? 3 : 1, num_hidden, x_layout, dys, X, W, fb, dX, partial, B, out_dim, activation, wgrid, s,
+            prof.start(), prof.stop(), recompute_for(num_hidden) || io16, io16);
     } else if (fused) {
         (void)bb;
         if (num_hidden == 1) { if (x_layout == 0) MLP32_BF2(1, 0); else MLP32_BF2(1, 1); }
@@ -1205,32 +1195,24 @@ static int mlp32_backward_impl(const float* dY, const float* X, WSrc W, const fl
 #undef MLP32_BWD2
 #undef MLP32_BA
     if (defer) {
-        g_pending = ReduceJob{partial, wgrid, NW, dW, 0};
-        g_have_pending = true;
+        const ReduceJob mine = {partial, wgrid, NW, dW, 0};
+        static_assert(sizeof(mine) <= sizeof(pair->job), "common.h DeferredReduce holds a ReduceJob");
+        memcpy(pair->job, &mine, sizeof(mine));
+        pair->filled = true;
     } else {
-        // enerf_mlp32_signal_next_reduce: the reduce launch carries the signal event as its stop event -- a
-        // kernel-attached completion signal costs the stream nothing, where an event record after the launch is a
-        // packet of its own that the next kernel waits for (tools/launch_chain.hip: +0 against +3 us per kernel)
-        hipEvent_t sig = nullptr;
-        if (g_signal_armed) {
-            g_signal_armed = false;
-            // (tried and dropped, tools/step_timeline.py: a device-scope release event -- same ~6 us before the next
-            // kernel of this stream; a generation number published by the reduce launch's last workgroup + a sleeping
-            // wait kernel on the other stream -- the gap goes, the reduce launch grows by 3 us, the step does not move)
-            if (!g_signal_event && hipEventCreateWithFlags(&g_signal_event, kSignalEventFlags) != hipSuccess)
-                g_signal_event = nullptr;
-            sig = g_signal_event;
-            g_signal_recorded = sig != nullptr;
-        }
+        const hipEvent_t sig = signal ? signal_event() : nullptr;
         ProfScope prof_reduce(ENERF_K_MLP_REDUCE, s);
-        if (g_have_pending) {
-            g_have_pending = false;
-            hipExtLaunchKernelGGL(k_mlp32_reduce_w2, dim3(div_up(g_pending.NW, 64) + div_up(NW, 64)), dim3(1024), 0, s,
-                                  nullptr, sig, 0, g_pending, ReduceJob{partial, wgrid, NW, dW, 0}, amp_state().found_inf);
+        if (pair) {
+            ReduceJob first;
+            memcpy(&first, pair->job, sizeof(first));
+            pair->filled = false;
+            hipExtLaunchKernelGGL(k_mlp32_reduce_w2, dim3(div_up(first.NW, 64) + div_up(NW, 64)), dim3(1024), 0, s, nullptr,
+                                  sig, 0, first, ReduceJob{partial, wgrid, NW, dW, 0}, amp_state().found_inf);
         } else {
             hipExtLaunchKernelGGL(k_mlp32_reduce_w, dim3(div_up(NW, 64)), dim3(1024), 0, s, nullptr, sig, 0, partial,
                                   wgrid, NW, dW, amp_state().found_inf);
         }
+        if (sig && signalled) *signalled = sig;
     }
     ENERF_LAUNCH_CHECK("mlp32_backward");
     return 0;
@@ -1244,17 +1226,17 @@ static uint64_t g_nerf_built_gen = 0;
 static uint32_t g_nerf_map_cols = 0, g_nerf_map_out = 0;      // geometry nerf_launch_frag_map's table was made for
 static uint64_t g_nerf_map_gen = ~0ull;
 
-// 1 when enerf_nerf_mlp_forward / _backward serve the process's current arithmetic (split-bf16, recomputing backward)
-int enerf_nerf_mlp_available(void) { return (g_nerf_fused && g_precision == 1 && g_recompute && g_fused_bwd) ? 1 : 0; }
+// common.h: whether nerf_mlp_forward / _backward serve arithmetic `mode` (split-bf16, recomputing backward)
+bool enerf::nerf_mlp_available(int mode) { return g_nerf_fused && mode == 1 && g_recompute && g_fused_bwd; }
 // testing aid: 0 = callers that ask enerf_nerf_mlp_available() fall back to one launch per net; returns the previous value
-int enerf_debug_nerf_mlp_fused(int on) {
+extern "C" int enerf_debug_nerf_mlp_fused(int on) {
     const int prev = g_nerf_fused ? 1 : 0;
     if (on >= 0) g_nerf_fused = on != 0;
     return prev;
 }
 
 static int nerf_args_ok(const float* const* wseg_s, const float* const* wseg_c, uint32_t w0_cols_c, uint32_t out_c,
-                        const char* what) {
+                        int mode, const char* what) {
     if (!wseg_s || !wseg_c || !wseg_s[0] || !wseg_s[3] || !wseg_c[0] || !wseg_c[1] || !wseg_c[3]) {
         set_error("%s: weight segments {first layer, hidden 0, -, output layer} of both nets are required", what);
         return ENERF_E_BADARG;
@@ -1267,11 +1249,21 @@ static int nerf_args_ok(const float* const* wseg_s, const float* const* wseg_c, 
         set_error("%s: colour outputs must be in [1, 16], got %u", what, out_c);
         return ENERF_E_BADARG;
     }
-    if (g_precision != 1) {
+    if (mode != 1) {
         set_error("%s: serves the split-bf16 arithmetic (enerf_mlp32_precision 1) only; ask enerf_nerf_mlp_available()", what);
         return ENERF_E_BADARG;
     }
     return 0;
+}
+
+// where the reduce pass writes the two nets' weight gradients
+static void nerf_dsts(float* const* dwseg_s, float* const* dwseg_c, uint32_t w0_cols_c, uint32_t overwrite, WDst* ds, WDst* dc) {
+    for (int k = 0; k < 4; k++) {
+        ds->seg[k] = (k == 0 || k == 3) ? dwseg_s[k] : nullptr;
+        dc->seg[k] = (k == 0 || k == 1 || k == 3) ? dwseg_c[k] : nullptr;
+    }
+    ds->w0_cols = IN; ds->nerf_perm = 0; ds->overwrite = overwrite;
+    dc->w0_cols = w0_cols_c; dc->nerf_perm = 1; dc->overwrite = overwrite;
 }
 
 // the operand fragments of the five matrices (flags bit 0: the caller vouches that they were built for these very
@@ -1295,12 +1287,12 @@ static uint32_t* nerf_frags(const float* const* wseg_s, const float* const* wseg
 }
 
 // feats [16, Bp, 2] (grid_encode_forward's level-major layout 2), dirs [B, 3] -> sigma [B] = exp(h0), rgb [B, out_c] =
-// sigmoid(colour net([h0 | geo_feat | SH(dirs)])).  Honours enerf_mlp32_valid_rows.
-int enerf_nerf_mlp_forward(const float* feats, const float* dirs, const float* const* wseg_s, const float* const* wseg_c,
-                           uint32_t w0_cols_c, uint32_t B, uint32_t out_c, float* sigma, float* rgb, uint32_t flags,
-                           enerf_stream_t stream) {
+// sigmoid(colour net([h0 | geo_feat | SH(dirs)])).  (common.h: enerf_nerf_mlp_forward with its modifiers)
+int enerf::nerf_mlp_forward(const float* feats, const float* dirs, const float* const* wseg_s, const float* const* wseg_c,
+                            uint32_t w0_cols_c, uint32_t B, uint32_t out_c, float* sigma, float* rgb, uint32_t flags,
+                            enerf_stream_t stream, const MlpCall& c) {
     if (B == 0) return 0;
-    if (int e = nerf_args_ok(wseg_s, wseg_c, w0_cols_c, out_c, "nerf_mlp_forward")) return e;
+    if (int e = nerf_args_ok(wseg_s, wseg_c, w0_cols_c, out_c, c.mode, "nerf_mlp_forward")) return e;
     if (!feats || !dirs || !sigma || !rgb) ENERF_BADARG("nerf_mlp_forward: feats, dirs, sigma and rgb are required");
     if (int eg = single_device_guard("nerf_mlp_forward")) return eg;
     hipStream_t s = (hipStream_t)stream;
@@ -1309,21 +1301,22 @@ int enerf_nerf_mlp_forward(const float* feats, const float* dirs, const float* c
     if (!frags) return ENERF_E_NOMEM;
     ProfScope prof(ENERF_K_FFMLP_FWD, s, true);
     prof.units((double)B);
-    nerf_launch_fwd(feats, dirs, frags, sigma, rgb, B, out_c, g_valid_rows, g_valid_base, g_valid_cap,
+    nerf_launch_fwd(feats, dirs, frags, sigma, rgb, B, out_c, c.rows.count, c.rows.base, c.rows.cap,
                     pgrid(B, g_fwd_blocks ? g_fwd_blocks : kNerfFwdPerCu * num_cus()), s, prof.start(), prof.stop());
     ENERF_LAUNCH_CHECK("nerf_mlp_forward");
     return 0;
 }
 
 // Gradients of both nets' weights (dwseg_*: overwritten when `overwrite`, else added to) and of feats (dfeat [16, Bp, 2])
-// given g_rgb [B, out_c], g_sigma [B] (multiplied by sigma_scale on the fly) and the forward's rgb.  Honours
-// enerf_mlp32_valid_rows and enerf_mlp32_signal_next_reduce (the reduce launch carries the signal).
-int enerf_nerf_mlp_backward(const float* g_rgb, const float* g_sigma, float sigma_scale, const float* feats,
-                            const float* dirs, const float* rgb, const float* const* wseg_s, const float* const* wseg_c,
-                            float* const* dwseg_s, float* const* dwseg_c, uint32_t w0_cols_c, uint32_t overwrite,
-                            uint32_t B, uint32_t out_c, float* dfeat, uint32_t flags, enerf_stream_t stream) {
+// given g_rgb [B, out_c], g_sigma [B] (multiplied by sigma_scale on the fly) and the forward's rgb.  (common.h:
+// enerf_nerf_mlp_backward with its modifiers; `signal`: the last launch carries the completion signal, *signalled is the event)
+int enerf::nerf_mlp_backward(const float* g_rgb, const float* g_sigma, float sigma_scale, const float* feats,
+                             const float* dirs, const float* rgb, const float* const* wseg_s, const float* const* wseg_c,
+                             float* const* dwseg_s, float* const* dwseg_c, uint32_t w0_cols_c, uint32_t overwrite,
+                             uint32_t B, uint32_t out_c, float* dfeat, uint32_t flags, enerf_stream_t stream,
+                             const MlpCall& c, bool signal, hipEvent_t* signalled) {
     if (B == 0) return 0;
-    if (int e = nerf_args_ok(wseg_s, wseg_c, w0_cols_c, out_c, "nerf_mlp_backward")) return e;
+    if (int e = nerf_args_ok(wseg_s, wseg_c, w0_cols_c, out_c, c.mode, "nerf_mlp_backward")) return e;
     if (!dwseg_s || !dwseg_c || !dwseg_s[0] || !dwseg_s[3] || !dwseg_c[0] || !dwseg_c[1] || !dwseg_c[3])
         ENERF_BADARG("nerf_mlp_backward: gradient segments of both nets are required");
     if (!g_rgb || !g_sigma || !feats || !dirs || !rgb || !dfeat)
@@ -1336,15 +1329,9 @@ int enerf_nerf_mlp_backward(const float* g_rgb, const float* g_sigma, float sigm
     const uint32_t grid = pgrid(B, g_bwd_blocks ? g_bwd_blocks : 256);
     float* partial = (float*)workspace(WS_NERF_PART, sizeof(float) * (size_t)grid * kNerfPartialStride);
     if (!partial) return ENERF_E_NOMEM;
-    hipEvent_t sig = nullptr;
+    const hipEvent_t sig = signal ? signal_event() : nullptr;
+    if (sig && signalled) *signalled = sig;
     bool sig_sent = false;
-    if (g_signal_armed) {
-        g_signal_armed = false;
-        if (!g_signal_event && hipEventCreateWithFlags(&g_signal_event, kSignalEventFlags) != hipSuccess)
-            g_signal_event = nullptr;
-        sig = g_signal_event;
-        g_signal_recorded = sig != nullptr;
-    }
     {
         ProfScope prof(ENERF_K_FFMLP_BWD, s, true);
         prof.units((double)B);
@@ -1355,16 +1342,11 @@ int enerf_nerf_mlp_backward(const float* g_rgb, const float* g_sigma, float sigm
             stop = sig;
             sig_sent = true;
         }
-        nerf_launch_bwd(feats, dirs, g_rgb, rgb, g_sigma, sigma_scale, frags, dfeat, partial, B, out_c, g_valid_rows,
-                        g_valid_base, g_valid_cap, grid, s, prof.start(), stop);
+        nerf_launch_bwd(feats, dirs, g_rgb, rgb, g_sigma, sigma_scale, frags, dfeat, partial, B, out_c, c.rows.count,
+                        c.rows.base, c.rows.cap, grid, s, prof.start(), stop);
     }
     WDst ds, dc;
-    for (int k = 0; k < 4; k++) {
-        ds.seg[k] = (k == 0 || k == 3) ? dwseg_s[k] : nullptr;
-        dc.seg[k] = (k == 0 || k == 1 || k == 3) ? dwseg_c[k] : nullptr;
-    }
-    ds.w0_cols = IN; ds.nerf_perm = 0; ds.overwrite = overwrite;
-    dc.w0_cols = w0_cols_c; dc.nerf_perm = 1; dc.overwrite = overwrite;
+    nerf_dsts(dwseg_s, dwseg_c, w0_cols_c, overwrite, &ds, &dc);
     if (flags & 2u) {
         // the caller sums the partial sums itself (enerf::nerf_mlp_partial_job): no reduce launch; the signal leaves on a
         // marker of its own
@@ -1382,6 +1364,55 @@ int enerf_nerf_mlp_backward(const float* g_rgb, const float* g_sigma, float sigm
     return 0;
 }
 
+// common.h: enerf_mlp32_backward_p with its modifiers.  Weights and weight gradients where the caller keeps them (see
+// mlp32_forward_p); overwrite != 0: dwseg receives the gradient (no zero-filled accumulator needed), else it is added to.
+int enerf::mlp32_backward_p(const float* dY, const float* X, const float* const* wseg, float* const* dwseg,
+                            uint32_t w0_cols, uint32_t nerf_perm, uint32_t overwrite, const float* fb, uint32_t B,
+                            uint32_t in_dim, uint32_t out_dim, uint32_t num_hidden, uint32_t activation, float* bb,
+                            float* dX, uint32_t x_layout, uint32_t dy_stride, const float* y_sigmoid,
+                            uint32_t y_sigmoid_stride, const float* dsigma, const float* h0, uint32_t h0_stride,
+                            enerf_stream_t stream, const MlpCall& c, bool signal, hipEvent_t* signalled,
+                            DeferredReduce* pair) {
+    if (num_hidden < 1 || num_hidden > 3) ENERF_BADARG("mlp32: num_hidden must be 1..3, got %u", num_hidden);
+    if (int e = segs_ok((const void* const*)wseg, num_hidden, w0_cols, nerf_perm, "mlp32_backward_p")) return e;
+    if (int e = segs_ok((const void* const*)dwseg, num_hidden, w0_cols, nerf_perm, "mlp32_backward_p (gradients)")) return e;
+    if (c.io16 && c.mode != 3) ENERF_BADARG("mlp32_backward_p: 16-bit I/O (enerf_mlp32_io16) serves precision 3 only");
+    if (c.io16 && (num_hidden < 2 || out_dim > 16 || x_layout != 0 || !g_fused_bwd))
+        ENERF_BADARG("mlp32_backward_p: 16-bit I/O needs two or three hidden layers, out_dim <= 16, row-major X and the "
+                     "fused backward");
+    return mlp32_backward_impl(dY, X, seg_src(wseg, num_hidden, w0_cols, nerf_perm, c.rows), fb, B, in_dim, out_dim, num_hidden,
+                               activation, bb, dX, seg_dst(dwseg, num_hidden, w0_cols, nerf_perm, overwrite), x_layout, dy_stride,
+                               y_sigmoid, y_sigmoid_stride, dsigma, h0, h0_stride, stream, c.mode, c.io16, signal, signalled,
+                               pair);
+}
+
+// ---- the public calls: the forms above under the process's settings ----------------------------------------------------
+// One public call's modifiers, assembled from the settings (`p_form`: an enerf_mlp32_*_p call, which enerf_mlp32_io16 serves)
+struct PublicCall {
+    MlpCall c;
+    bool signal;
+    hipEvent_t signalled;
+    DeferredReduce* pair;
+};
+static PublicCall public_call(bool p_form = false) {
+    return {{g_valid, g_precision, p_form && g_io16_p}, g_signal_armed, nullptr,
+            (g_defer_next || g_pending.filled) ? &g_pending : nullptr};
+}
+// ... and the one-shots it consumed: the signal by the launch that carried it, the deferral by the call that left its sums.
+// (A call that fails between argument validation and its launches -- no workspace, no event -- leaves both armed, where
+// the globals used to be cleared on the way in; what the header documents is the same: the next call that does launch
+// consumes them, and enerf_stream_wait_mlp32_signal refuses until one has.)
+static int public_done(const PublicCall& p, int rc) {
+    if (p.signalled) {
+        g_signal_armed = false;
+        g_signal_recorded = true;
+    }
+    if (p.pair && p.pair->filled) g_defer_next = false;
+    return rc;
+}
+
+extern "C" {
+
 int enerf_mlp32_signal_next_reduce(int on) {
     g_signal_armed = on != 0;
     if (on) g_signal_recorded = false;
@@ -1396,8 +1427,33 @@ int enerf_stream_wait_mlp32_signal(enerf_stream_t stream) {
 
 int enerf_mlp32_defer_reduce(int on) {
     g_defer_next = on != 0;
-    g_have_pending = false;        // a pair always starts here: sums left behind by a pair that never completed are dropped
+    g_pending.filled = false;      // a pair always starts here: sums left behind by a pair that never completed are dropped
     return 0;
+}
+
+int enerf_mlp32_forward(const float* X, const float* W, uint32_t B, uint32_t in_dim, uint32_t out_dim,
+                        uint32_t num_hidden, uint32_t activation, uint32_t output_activation, float* fb, float* Y,
+                        uint32_t x_layout, uint32_t y_stride, float* y0_exp, enerf_stream_t stream) {
+    return enerf_mlp32_forward_sh(X, W, B, in_dim, out_dim, num_hidden, activation, output_activation, fb, Y, x_layout, y_stride,
+                                  y0_exp, nullptr, stream);
+}
+
+int enerf_mlp32_forward_sh(const float* X, const float* W, uint32_t B, uint32_t in_dim, uint32_t out_dim,
+                           uint32_t num_hidden, uint32_t activation, uint32_t output_activation, float* fb, float* Y,
+                           uint32_t x_layout, uint32_t y_stride, float* y0_exp, const float* sh_dirs,
+                           enerf_stream_t stream) {
+    if (num_hidden < 1 || num_hidden > 3) ENERF_BADARG("mlp32: num_hidden must be 1..3, got %u", num_hidden);
+    const PublicCall p = public_call();
+    return mlp32_forward_impl(X, blob_src(W, num_hidden, p.c.rows), B, in_dim, out_dim, num_hidden, activation,
+                              output_activation, fb, Y, x_layout, y_stride, y0_exp, sh_dirs, stream, p.c.mode, false);
+}
+
+int enerf_mlp32_forward_p(const float* X, const float* const* wseg, uint32_t w0_cols, uint32_t nerf_perm, uint32_t B,
+                          uint32_t in_dim, uint32_t out_dim, uint32_t num_hidden, uint32_t activation,
+                          uint32_t output_activation, float* fb, float* Y, uint32_t x_layout, uint32_t y_stride,
+                          float* y0_exp, const float* sh_dirs, enerf_stream_t stream) {
+    return mlp32_forward_p(X, wseg, w0_cols, nerf_perm, B, in_dim, out_dim, num_hidden, activation, output_activation, fb, Y,
+                           x_layout, y_stride, y0_exp, sh_dirs, stream, public_call(true).c);
 }
 
 int enerf_mlp32_backward(const float* dY, const float* X, const float* W, const float* fb, uint32_t B, uint32_t in_dim,
@@ -1405,52 +1461,42 @@ int enerf_mlp32_backward(const float* dY, const float* X, const float* W, const 
                          uint32_t x_layout, uint32_t dy_stride, const float* y_sigmoid, uint32_t y_sigmoid_stride,
                          const float* dsigma, const float* h0, uint32_t h0_stride, enerf_stream_t stream) {
     if (num_hidden < 1 || num_hidden > 3) ENERF_BADARG("mlp32: num_hidden must be 1..3, got %u", num_hidden);
-    const WSrc w = blob_src(W, num_hidden);
-    WDst d;
-    for (int k = 0; k < 4; k++) d.seg[k] = w.seg[k] ? dW + (w.seg[k] - W) : nullptr;
-    d.w0_cols = IN;
-    d.nerf_perm = 0;
-    d.overwrite = 0;
-    return mlp32_backward_impl(dY, X, w, fb, B, in_dim, out_dim, num_hidden, activation, bb, dX, d, x_layout, dy_stride,
-                               y_sigmoid, y_sigmoid_stride, dsigma, h0, h0_stride, stream);
+    PublicCall p = public_call();
+    return public_done(p, mlp32_backward_impl(dY, X, blob_src(W, num_hidden, p.c.rows), fb, B, in_dim, out_dim, num_hidden,
+                                              activation, bb, dX, blob_dst(dW, num_hidden, 0), x_layout, dy_stride, y_sigmoid,
+                                              y_sigmoid_stride, dsigma, h0, h0_stride, stream, p.c.mode, false, p.signal,
+                                              &p.signalled, p.pair));
 }
 
-// The backward with weights and weight gradients where the caller keeps them (see enerf_mlp32_forward_p); overwrite != 0:
-// dwseg receives the gradient (no zero-filled accumulator needed), else it is added to.
 int enerf_mlp32_backward_p(const float* dY, const float* X, const float* const* wseg, float* const* dwseg,
                            uint32_t w0_cols, uint32_t nerf_perm, uint32_t overwrite, const float* fb, uint32_t B,
                            uint32_t in_dim, uint32_t out_dim, uint32_t num_hidden, uint32_t activation, float* bb,
                            float* dX, uint32_t x_layout, uint32_t dy_stride, const float* y_sigmoid,
                            uint32_t y_sigmoid_stride, const float* dsigma, const float* h0, uint32_t h0_stride,
                            enerf_stream_t stream) {
-    if (num_hidden < 1 || num_hidden > 3) ENERF_BADARG("mlp32: num_hidden must be 1..3, got %u", num_hidden);
-    if (int e = segs_ok((const void* const*)wseg, num_hidden, w0_cols, nerf_perm, "mlp32_backward_p")) return e;
-    if (int e = segs_ok((const void* const*)dwseg, num_hidden, w0_cols, nerf_perm, "mlp32_backward_p (gradients)")) return e;
-    WSrc w;
-    WDst d;
-    for (int k = 0; k < 4; k++) {
-        const bool used = k == 0 || k == 3 || (uint32_t)k < num_hidden;
-        w.seg[k] = used ? wseg[k] : nullptr;
-        d.seg[k] = used ? dwseg[k] : nullptr;
-    }
-    w.w0_cols = d.w0_cols = w0_cols;
-    w.nerf_perm = d.nerf_perm = nerf_perm;
-    w.valid_rows = g_valid_rows;
-    w.valid_base = g_valid_base;
-    w.valid_cap = g_valid_cap;
-    d.overwrite = overwrite;
-    if (!g_io16_p)
-        return mlp32_backward_impl(dY, X, w, fb, B, in_dim, out_dim, num_hidden, activation, bb, dX, d, x_layout, dy_stride,
-                                   y_sigmoid, y_sigmoid_stride, dsigma, h0, h0_stride, stream);
-    if (g_precision != 3) ENERF_BADARG("mlp32_backward_p: 16-bit I/O (enerf_mlp32_io16) serves precision 3 only");
-    if (num_hidden < 2 || out_dim > 16 || x_layout != 0 || !g_fused_bwd)
-        ENERF_BADARG("mlp32_backward_p: 16-bit I/O needs two or three hidden layers, out_dim <= 16, row-major X and the "
-                     "fused backward");
-    g_io16 = true;
-    const int rc = mlp32_backward_impl(dY, X, w, fb, B, in_dim, out_dim, num_hidden, activation, bb, dX, d, x_layout,
-                                       dy_stride, y_sigmoid, y_sigmoid_stride, dsigma, h0, h0_stride, stream);
-    g_io16 = false;
-    return rc;
+    PublicCall p = public_call(true);
+    return public_done(p, mlp32_backward_p(dY, X, wseg, dwseg, w0_cols, nerf_perm, overwrite, fb, B, in_dim, out_dim, num_hidden,
+                                           activation, bb, dX, x_layout, dy_stride, y_sigmoid, y_sigmoid_stride, dsigma, h0,
+                                           h0_stride, stream, p.c, p.signal, &p.signalled, p.pair));
+}
+
+// 1 when enerf_nerf_mlp_forward / _backward serve the process's current arithmetic
+int enerf_nerf_mlp_available(void) { return nerf_mlp_available(public_call().c.mode) ? 1 : 0; }
+
+// Both honour enerf_mlp32_valid_rows, the backward enerf_mlp32_signal_next_reduce as well (its last launch carries the signal).
+int enerf_nerf_mlp_forward(const float* feats, const float* dirs, const float* const* wseg_s, const float* const* wseg_c,
+                           uint32_t w0_cols_c, uint32_t B, uint32_t out_c, float* sigma, float* rgb, uint32_t flags,
+                           enerf_stream_t stream) {
+    return nerf_mlp_forward(feats, dirs, wseg_s, wseg_c, w0_cols_c, B, out_c, sigma, rgb, flags, stream, public_call().c);
+}
+
+int enerf_nerf_mlp_backward(const float* g_rgb, const float* g_sigma, float sigma_scale, const float* feats,
+                            const float* dirs, const float* rgb, const float* const* wseg_s, const float* const* wseg_c,
+                            float* const* dwseg_s, float* const* dwseg_c, uint32_t w0_cols_c, uint32_t overwrite,
+                            uint32_t B, uint32_t out_c, float* dfeat, uint32_t flags, enerf_stream_t stream) {
+    PublicCall p = public_call();
+    return public_done(p, nerf_mlp_backward(g_rgb, g_sigma, sigma_scale, feats, dirs, rgb, wseg_s, wseg_c, dwseg_s, dwseg_c,
+                                            w0_cols_c, overwrite, B, out_c, dfeat, flags, stream, p.c, p.signal, &p.signalled));
 }
 
 }  // extern "C"
@@ -1497,12 +1543,7 @@ int enerf::nerf_mlp_partial_job(float* const* dwseg_s, float* const* dwseg_c, ui
     for (int k = 0; k < 12; k++) same = same && g_part_key[k] == key[k];
     if (!same) {
         WDst ds, dc;
-        for (int k = 0; k < 4; k++) {
-            ds.seg[k] = (k == 0 || k == 3) ? dwseg_s[k] : nullptr;
-            dc.seg[k] = (k == 0 || k == 1 || k == 3) ? dwseg_c[k] : nullptr;
-        }
-        ds.w0_cols = IN; ds.nerf_perm = 0; ds.overwrite = 1;
-        dc.w0_cols = w0_cols_c; dc.nerf_perm = 1; dc.overwrite = 1;
+        nerf_dsts(dwseg_s, dwseg_c, w0_cols_c, 1, &ds, &dc);
         SmallDst sm;
         for (int k = 0; k < 5; k++) { sm.g[k] = small_g[k]; sm.n[k] = small_n[k]; }
         hipLaunchKernelGGL(k_nerf_partial_map, dim3(div_up(kNerfSigmaWords + nw_c, 256)), dim3(256), 0, s, ds, dc,
@@ -1521,7 +1562,7 @@ int enerf::nerf_mlp_partial_job(float* const* dwseg_s, float* const* dwseg_c, ui
 // common.h: the fragments' build handed to a launch that runs before the MLP forward on `s`
 int enerf::nerf_mlp_frag_job(const float* const* wseg_s, const float* const* wseg_c, uint32_t w0_cols_c, uint32_t out_c,
                              hipStream_t s, SplitJob* job) {
-    if (int e = nerf_args_ok(wseg_s, wseg_c, w0_cols_c, out_c, "nerf_mlp_frag_job")) return e;
+    if (int e = nerf_args_ok(wseg_s, wseg_c, w0_cols_c, out_c, 1, "nerf_mlp_frag_job")) return e;
     if (int ew = workspace_family_enter(1, s)) return ew;
     uint32_t* frags = (uint32_t*)workspace(WS_NERF_FRAGS, kNerfWsBytes);
     if (!frags) return ENERF_E_NOMEM;
@@ -1551,40 +1592,25 @@ void enerf::nerf_mlp_frags_built(const SplitJob& job, uint32_t w0_cols_c, uint32
 
 namespace enerf_mlp32 {
 
-// The reference's FFMLP entry points on this file's data flow (mlp32_common.h).  The arithmetic mode and the 16-bit I/O
-// flag are set for the duration of the call.
+// The reference's FFMLP entry points on this file's data flow (mlp32_common.h): public calls whose arithmetic mode follows
+// from `dtype` and whose X / Y / dY / dX are 16-bit.
 int ffmlp16_forward(int dtype, const void* X, const float* W32, uint32_t B, uint32_t num_hidden, uint32_t activation,
                     void* Y, hipStream_t s) {
     if (num_hidden < 2 || num_hidden > 3) ENERF_BADARG("ffmlp16_forward: two or three hidden layers");
-    const int prev = g_precision;
-    g_precision = dtype == ENERF_BF16 ? 2 : 3;
-    g_io16 = true;
-    const int rc = mlp32_forward_impl(reinterpret_cast<const float*>(X), blob_src(W32, num_hidden), B, IN, 16, num_hidden,
-                                      activation, 6, nullptr, reinterpret_cast<float*>(Y), 0, 16, nullptr, nullptr,
-                                      (enerf_stream_t)s);
-    g_io16 = false;
-    g_precision = prev;
-    return rc;
+    return mlp32_forward_impl(reinterpret_cast<const float*>(X), blob_src(W32, num_hidden, public_call().c.rows), B, IN, 16,
+                              num_hidden, activation, 6, nullptr, reinterpret_cast<float*>(Y), 0, 16, nullptr, nullptr,
+                              (enerf_stream_t)s, dtype == ENERF_BF16 ? 2 : 3, true);
 }
 
 int ffmlp16_backward(int dtype, const void* dY, const void* X, const float* W32, uint32_t B, uint32_t num_hidden,
                      uint32_t activation, void* dX, float* dW32, hipStream_t s) {
     if (num_hidden < 2 || num_hidden > 3) ENERF_BADARG("ffmlp16_backward: two or three hidden layers");
-    const WSrc w = blob_src(W32, num_hidden);
-    WDst d;
-    for (int k = 0; k < 4; k++) d.seg[k] = w.seg[k] ? dW32 + (w.seg[k] - W32) : nullptr;
-    d.w0_cols = IN;
-    d.nerf_perm = 0;
-    d.overwrite = 1;
-    const int prev = g_precision;
-    g_precision = dtype == ENERF_BF16 ? 2 : 3;
-    g_io16 = true;
-    const int rc = mlp32_backward_impl(reinterpret_cast<const float*>(dY), reinterpret_cast<const float*>(X), w, nullptr, B,
-                                       IN, 16, num_hidden, activation, nullptr, reinterpret_cast<float*>(dX), d, 0, 16,
-                                       nullptr, 0, nullptr, nullptr, 0, (enerf_stream_t)s);
-    g_io16 = false;
-    g_precision = prev;
-    return rc;
+    PublicCall p = public_call();
+    return public_done(p, mlp32_backward_impl(reinterpret_cast<const float*>(dY), reinterpret_cast<const float*>(X),
+                                              blob_src(W32, num_hidden, p.c.rows), nullptr, B, IN, 16, num_hidden, activation,
+                                              nullptr, reinterpret_cast<float*>(dX), blob_dst(dW32, num_hidden, 1), 0, 16,
+                                              nullptr, 0, nullptr, nullptr, 0, (enerf_stream_t)s, dtype == ENERF_BF16 ? 2 : 3,
+                                              true, p.signal, &p.signalled, p.pair));
 }
 
 }  // namespace enerf_mlp32

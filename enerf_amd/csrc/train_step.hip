@@ -17,8 +17,9 @@
 // The NEXT batch's march runs on the side stream behind the MLP backward, whose last launch carries the signal that stream
 // waits for (marches_side), or without a second stream: its count pass rides in the optimizer's launch, scan + write follow
 // it (marches_begin, optimizer).  What rides in another kernel's launch -- the fragments' build, the weight-gradient sums,
-// the count passes -- is an argument of that launch's internal entry point (common.h) and a local value here; only the public
-// one-shots that the Python-driven route uses as well are armed, through the Step object, which disarms on the way out.
+// the count passes -- and what modifies an MLP launch -- the rows that count, the arithmetic mode, the completion signal, the
+// two nets' shared reduce launch -- is an argument of that launch's internal entry point (common.h) and a local value here:
+// the step neither reads nor changes the process's enerf_mlp32_* settings, bar the arithmetic mode where mlp_precision < 0.
 #include <hip/hip_runtime.h>
 
 #include <chrono>
@@ -49,12 +50,12 @@ extern "C" int enerf_debug_carry_count(int on) {
 
 namespace {
 
-// The public one-shots of a step: process-global requests in mlp32.hip / raymarching.hip that the next matching library
-// call consumes.  One method arms each and remembers it; the destructor disarms what is still armed, so a step that returns
-// early leaves nothing behind for the next, unrelated call.  And what one function of the step hands a later one.
+// What one function of the step hands a later one, and the host timer.
 class Step {
 public:
+    int mode;                              // the MLP launches' arithmetic: the call's mlp_precision, or the process's
     bool fused;                            // both nets as one launch each way (csrc/nerf_mlp.hip: the split-bf16 default)
+    hipEvent_t signalled = nullptr;        // the event the MLP backward's last launch carried, for the side stream to wait on
     // for the optimizer's launch: the fused backward's weight-gradient partial sums (has_sums) ...
     PartialSums sums{nullptr, nullptr, 0, 0, 0};
     bool has_sums = false;
@@ -65,8 +66,8 @@ public:
 
     template <class A>
     Step(const A* a, bool timed) : timed_(timed) {
-        if (a->mlp_precision >= 0) prev_prec_ = enerf_mlp32_precision(a->mlp_precision);
-        fused = a->nh_s == 1 && a->nh_c == 2 && enerf_nerf_mlp_available() != 0;
+        mode = (a->mlp_precision >= 0 && a->mlp_precision <= 3) ? a->mlp_precision : enerf_mlp32_precision(-1);
+        fused = a->nh_s == 1 && a->nh_c == 2 && nerf_mlp_available(mode);
         if (timed_) {
             g_host_steps++;
             t_prev_ = std::chrono::steady_clock::now();
@@ -75,13 +76,10 @@ public:
     Step(const Step&) = delete;
     Step& operator=(const Step&) = delete;
     ~Step() {
-        // (one-shot march requests never outlive the step they were armed for -- csrc/raymarching.hip: MarchOneShot)
+        // (the one-shot march requests the caller may have armed for this step's own march never outlive it --
+        //  csrc/raymarching.hip: MarchOneShot)
         enerf_march_fuse_near_far(nullptr, 0.0f);
         enerf_march_mirror_count(nullptr);
-        if (defer_) enerf_mlp32_defer_reduce(0);
-        if (signal_) enerf_mlp32_signal_next_reduce(0);
-        if (mlp_rows_) enerf_mlp32_valid_rows(nullptr);
-        if (prev_prec_ >= 0) enerf_mlp32_precision(prev_prec_);
     }
 
     // Every timed call of the step passes its result through here: the host time since the previous one goes to the call's
@@ -97,28 +95,7 @@ public:
         return rc;
     }
 
-    // (the budget's unfilled rows are skipped: real rows = base + min(*counter, cap), cap == 0: *counter; nullptr: all)
-    void mlp_rows(const int32_t* counter, uint32_t base, uint32_t cap) {
-        if (!counter) return;
-        enerf_mlp32_valid_rows_ex(counter, base, cap);
-        mlp_rows_ = true;
-    }
-    void mlp_rows_off() {
-        if (mlp_rows_) enerf_mlp32_valid_rows(nullptr);
-        mlp_rows_ = false;
-    }
-    void defer_reduce(bool on) {
-        enerf_mlp32_defer_reduce(on ? 1 : 0);
-        defer_ = on;
-    }
-    void signal_next_reduce(bool on) {
-        enerf_mlp32_signal_next_reduce(on ? 1 : 0);
-        signal_ = on;
-    }
-
 private:
-    int prev_prec_ = -1;
-    bool mlp_rows_ = false, defer_ = false, signal_ = false;
     bool timed_;
     int slot_ = 0;
     std::chrono::steady_clock::time_point t_prev_;
@@ -172,21 +149,17 @@ int forward(Step& st, const A* a, const Batch& b, bool carry, uint32_t frags) {
         nerf_mlp_frags_built(job, a->w0_cols_c, a->out_c);
         frags = 1;
     }
-    st.mlp_rows(b.counter, b.base, b.cap);
-    int rc;
-    if (st.fused) {
-        rc = st.run(enerf_nerf_mlp_forward(b.feats, b.dirs, a->wseg_s, a->wseg_c, a->w0_cols_c, b.rows, a->out_c, b.sigma, b.rgb,
-                                           frags, s),
-                    2);
-    } else {
-        rc = st.run(enerf_mlp32_forward_p(b.feats, a->wseg_s, 32, 0, b.rows, 32, 16, a->nh_s, 0, 6, b.fb_s, b.h32, 1, 32, b.sigma,
-                                          b.dirs, s));
-        if (!rc)
-            rc = st.run(enerf_mlp32_forward_p(b.h32, a->wseg_c, a->w0_cols_c, 1, b.rows, 32, a->out_c, a->nh_c, 0, 3, b.fb_c, b.rgb,
-                                              0, 0, nullptr, nullptr, s));
-    }
-    st.mlp_rows_off();
-    return rc;
+    // (the budget's unfilled rows are skipped by the MLP launches as by the grid's)
+    const MlpCall c = {{b.counter, b.base, b.cap}, st.mode, false};
+    if (st.fused)
+        return st.run(nerf_mlp_forward(b.feats, b.dirs, a->wseg_s, a->wseg_c, a->w0_cols_c, b.rows, a->out_c, b.sigma, b.rgb,
+                                       frags, s, c),
+                      2);
+    if (int rc = st.run(mlp32_forward_p(b.feats, a->wseg_s, 32, 0, b.rows, 32, 16, a->nh_s, 0, 6, b.fb_s, b.h32, 1, 32, b.sigma,
+                                        b.dirs, s, c)))
+        return rc;
+    return st.run(mlp32_forward_p(b.h32, a->wseg_c, a->w0_cols_c, 1, b.rows, 32, a->out_c, a->nh_c, 0, 3, b.fb_c, b.rgb, 0, 0,
+                                  nullptr, nullptr, s, c));
 }
 
 // `signal`: the last launch carries the signal the side stream's marches wait for; `fold`: the optimizer follows in this call
@@ -194,34 +167,27 @@ int forward(Step& st, const A* a, const Batch& b, bool carry, uint32_t frags) {
 template <class A>
 int backward(Step& st, const A* a, const Batch& b, bool signal, bool fold) {
     enerf_stream_t s = a->stream;
-    st.mlp_rows(b.counter, b.base, b.cap);
-    if (signal) st.signal_next_reduce(true);
-    int rc;
+    const MlpCall c = {{b.counter, b.base, b.cap}, st.mode, false};
     if (st.fused) {
         if (fold && g_fold_reduce)
             st.has_sums = nerf_mlp_partial_job(a->dwseg_s, a->dwseg_c, a->w0_cols_c, a->out_c, a->small_g, a->small_n, a->n_small,
                                                b.rows, (hipStream_t)s, &st.sums) == 0;
-        rc = st.run(enerf_nerf_mlp_backward(b.g_rgbs, b.g_sigmas, 1.0f, b.feats, b.dirs, b.rgb, a->wseg_s, a->wseg_c, a->dwseg_s,
-                                            a->dwseg_c, a->w0_cols_c, b.overwrite, b.rows, a->out_c, b.dfeat,
-                                            st.has_sums ? 3u : 1u, s),
-                    2);
-    } else {
-        st.defer_reduce(true);             // (the colour net's partial sums wait for the sigma net's reduce launch)
-        rc = st.run(enerf_mlp32_backward_p(b.g_rgbs, b.h32, a->wseg_c, a->dwseg_c, a->w0_cols_c, 1, b.overwrite, b.fb_c, b.rows,
-                                           32, a->out_c, a->nh_c, 0, nullptr, b.dx32, 0, 0, b.rgb, a->out_c, nullptr, nullptr, 0,
-                                           s));
-        if (!rc)
-            rc = st.run(enerf_mlp32_backward_p(b.dx32, b.feats, a->wseg_s, a->dwseg_s, 32, 0, b.overwrite, b.fb_s, b.rows, 32, 16,
-                                               a->nh_s, 0, nullptr, b.dfeat, 1, 32, nullptr, 0, b.g_sigmas, b.h32, 32, s));
-        st.defer_reduce(false);
+        return st.run(nerf_mlp_backward(b.g_rgbs, b.g_sigmas, 1.0f, b.feats, b.dirs, b.rgb, a->wseg_s, a->wseg_c, a->dwseg_s,
+                                        a->dwseg_c, a->w0_cols_c, b.overwrite, b.rows, a->out_c, b.dfeat, st.has_sums ? 3u : 1u,
+                                        s, c, signal, &st.signalled),
+                      2);
     }
-    st.mlp_rows_off();
-    if (signal) st.signal_next_reduce(false);
-    return rc;
+    DeferredReduce pair = {};              // (the colour net's partial sums wait for the sigma net's reduce launch)
+    if (int rc = st.run(mlp32_backward_p(b.g_rgbs, b.h32, a->wseg_c, a->dwseg_c, a->w0_cols_c, 1, b.overwrite, b.fb_c, b.rows, 32,
+                                         a->out_c, a->nh_c, 0, nullptr, b.dx32, 0, 0, b.rgb, a->out_c, nullptr, nullptr, 0, s, c,
+                                         false, nullptr, &pair)))
+        return rc;
+    return st.run(mlp32_backward_p(b.dx32, b.feats, a->wseg_s, a->dwseg_s, 32, 0, b.overwrite, b.fb_s, b.rows, 32, 16, a->nh_s, 0,
+                                   nullptr, b.dfeat, 1, 32, nullptr, 0, b.g_sigmas, b.h32, 32, s, c, signal, &st.signalled, &pair));
 }
 
 // The next marches carried by the optimizer's launch where that applies: all of them or none (st.counts).  Decided in front
-// of the MLP backward, because the side-stream form needs its signal armed there.
+// of the MLP backward, because the side-stream form has that call's last launch carry its signal.
 template <class A>
 int marches_begin(Step& st, const A* a, const NextMarch* next, uint32_t n, bool carry) {
     if (!carry || !g_carry_count || (a->march_flags & 16u)) return 0;
@@ -243,7 +209,9 @@ int marches_begin(Step& st, const A* a, const NextMarch* next, uint32_t n, bool 
 template <class A>
 int marches_side(Step& st, const A* a, const NextMarch* next, uint32_t n) {
     enerf_stream_t ss = a->side_stream;
-    if (int rc = st.run(enerf_stream_wait_mlp32_signal(ss))) return rc;
+    if (!st.signalled) ENERF_BADARG("train_step: no launch of the MLP backward carried the signal the side stream waits for");
+    if (int rc = st.run(check_hip(hipStreamWaitEvent((hipStream_t)ss, st.signalled, 0), "train_step: side stream wait")))
+        return rc;
     for (uint32_t q = 0; q < n; q++) {
         const NextMarch& m = next[q];
         // (near / far inside the march's count pass: one launch less at the head of the chain the next step waits for)

@@ -635,10 +635,13 @@ int enerf_adam_step_multi(uint32_t count, float* const* p, float* const* g, floa
  * march_rays_train_ex, grid_encode_backward_ex(defer), grid_adam_from_records_ex): results are those of the calls made
  * one by one.  What it removes is the host's work between the launches (nerf/utils.py:575-640 + main_nerf.py:211 run
  * ~60 framework calls per step).  All pointers are device pointers unless noted; every buffer is the caller's.
- * Scalar background (bg_scalar), density_scale 1, fp32 table with L = 16, C = 2, D = 3. */
+ * Scalar background (bg_scalar), density_scale 1, fp32 table with L = 16, C = 2, D = 3.
+ * The step's MLP launches take their valid rows from its own `counter` field (NULL: every row) and their arithmetic from its
+ * own `mlp_precision` field: the step neither consumes nor clears the process-wide enerf_mlp32_valid_rows,
+ * enerf_mlp32_signal_next_reduce or enerf_mlp32_defer_reduce requests, and leaves enerf_mlp32_precision as it is. */
 typedef struct enerf_train_step_args {
     uint32_t struct_bytes;              /* sizeof(enerf_train_step_args): checked */
-    int mlp_precision;                  /* enerf_mlp32_precision for this call's MLP launches; < 0: leave as is */
+    int mlp_precision;                  /* enerf_mlp32_precision's mode for this call's MLP launches; < 0: the process's */
     enerf_stream_t stream, side_stream; /* side_stream only used when next_rays_o != NULL */
     /* this batch: samples from march_rays_train (M rows budgeted, counter[0] real), N rays */
     uint32_t N, M;
@@ -719,7 +722,10 @@ int enerf_debug_march_carry_blocks(uint32_t blocks);
  * enerf_amd/events.train_step_events_manual + FusedAdam.step_grid_table issue): per render grid_encode_forward,
  * mlp32_forward_p x 2, composite_rays_train_forward_blend; event_loss_fwd_bwd; per render
  * composite_rays_train_backward_mse(target = NULL), mlp32_backward_p x 2 (the second render's weight gradients are
- * added to the first's), grid_encode_backward_ex(defer, reserve = M1 + M2); grid_adam_from_records_ex. */
+ * added to the first's), grid_encode_backward_ex(defer, reserve = M1 + M2); grid_adam_from_records_ex.
+ * As in enerf_train_step_mse, the MLP launches take their valid rows from the renders' own `counter` fields and their
+ * arithmetic from `mlp_precision`: the process-wide enerf_mlp32_valid_rows, enerf_mlp32_signal_next_reduce and
+ * enerf_mlp32_defer_reduce requests are neither consumed nor cleared. */
 typedef struct enerf_step_render {
     uint32_t N, M;                      /* rays, sample rows budgeted (counter[0] real) */
     const float *xyzs, *dirs, *deltas;
@@ -771,7 +777,7 @@ typedef struct enerf_event_step_args {
      * r[0]'s in one buffer, and the m_* pointers hold scratch for 2 M rows (shapes of the per-render scratch with 2 M
      * for M).  Then grid_encode_forward, the four mlp32 launches, grid_encode_backward run ONCE over the 2 M rows (rows
      * [counter0, M) are padding whose gradients the first render's composite backward zero-fills; the MLP kernels take
-     * M + min(counter1, M) as their valid-row count: enerf_mlp32_valid_rows_ex); compositing and its backward stay per
+     * M + min(counter1, M) as their valid-row count: enerf_mlp32_valid_rows_ex's rule); compositing and its backward stay per
      * render, on the halves.  Same per-sample values; the weight gradients are summed over both renders in one pass
      * instead of two passes added. */
     uint32_t flags, reserved;

@@ -1236,12 +1236,123 @@ def test_model_with_a_staged_ring_copy_deep_copies_and_saves():
         assert n == n2 and torch.equal(p, p2)
 
 
+def _seven_steps(model, h, data, around_native=None):
+    """Step 0 (Python-driven: the cold window's first) and six one-call steps -> (losses, counters); `around_native`
+    wraps every call of fused_render.train_step_native."""
+    from enerf_amd import fused_render
+    calls = []
+    orig = fused_render.train_step_native
+
+    def native(*a, **k):
+        calls.append(1)
+        return orig(*a, **k) if around_native is None else around_native(orig, *a, **k)
+
+    fused_render.train_step_native = native
+    try:
+        losses, counters = [], []
+        for i in range(7):
+            nxt = data[(i + 1) % 4]
+            losses.append(float(h.step_rgb(*data[i % 4], next_rays=(nxt[0], nxt[1]))))
+            counters.append(model.step_counter[model.rendered_counter_slot].cpu().clone())
+    finally:
+        fused_render.train_step_native = orig
+    torch.cuda.synchronize()
+    assert len(calls) == (6 if h.native_step else 0)
+    return np.array(losses), torch.stack(counters)
+
+
+def test_process_wide_row_count_does_not_reach_the_one_call_step():
+    """The one-call step's MLP launches take their rows from the call's own `counter` field and not from
+    enerf_mlp32_valid_rows: a count of 32 rows set process-wide in front of every one-call step changes neither the samples
+    nor the losses.  (Skipped rows are left unwritten in the step's own scratch: a step that honoured the setting would
+    train on stale values.)
+    With `counter` NULL -- what fused_render._fill_samples passes with SKIP_PADDING_ROWS off -- every row of the budget
+    counts.  Both one-call steps' compositing needs the counter and refuses such a call (so no step can be trained that
+    way, on any commit); what the forward has written by then shows the rows its launches took: sigma and rgb of ALL rows,
+    bit for bit what the same call writes with no process-wide count set.  (Before the MLP calls took their rows as an
+    argument, a NULL counter left the launches to the process's setting: 32 rows written, the rest stale.)"""
+    import ctypes
+    from enerf_amd import _lib as L
+    from enerf_amd.network import NeRFNetwork
+    from enerf_amd.trainer import TrainHarness
+    lib = L.lib()
+    data = _batches(4, 1024, 2)
+    t = torch.full((1,), 32, dtype=torch.int32, device=DEV)
+    runs = []
+    for armed in (False, True):
+        torch.manual_seed(0)
+        model = NeRFNetwork(encoding="hashgrid", bound=2, cuda_ray=True, out_dim_color=3).to(DEV)
+        h = TrainHarness(model, lr=1e-2, occupancy="synthetic")
+
+        def around(orig, *a, **k):
+            if armed:
+                lib.enerf_mlp32_valid_rows(t.data_ptr())
+            return orig(*a, **k)
+
+        try:
+            runs.append(_seven_steps(model, h, data, around))
+        finally:
+            lib.enerf_mlp32_valid_rows(None)
+    (la, ca), (lb, cb) = runs
+    assert torch.equal(ca, cb)
+    assert np.abs(la - lb).max() <= 1e-5 * np.abs(la).max(), (la, lb)
+    # the last call's arguments once more (buffers and batch are alive), without a counter and without a next march
+    a, bufs = model._native_ctx["a"], model._native_ctx["t"]
+    a.loss = a.counter = a.next_rays_o = None
+    outs = []
+    for armed in (False, True):
+        bufs["sigma"].fill_(-7.0)
+        bufs["rgb"].fill_(-7.0)
+        if armed:
+            lib.enerf_mlp32_valid_rows(t.data_ptr())
+        try:
+            rc = lib.enerf_train_step_mse(ctypes.byref(a))
+        finally:
+            lib.enerf_mlp32_valid_rows(None)
+        assert rc == -1 and b"counter" in lib.enerf_last_error()                # ENERF_E_BADARG, from the compositing
+        torch.cuda.synchronize()
+        outs.append((bufs["sigma"].clone(), bufs["rgb"].clone()))
+    for x, y in zip(*outs):                  # (sigma = exp(.) and rgb = sigmoid(.) are never negative: every row was written)
+        assert bool((x != -7.0).all()) and torch.equal(x.view(torch.int32), y.view(torch.int32))
+
+
+def test_one_call_step_runs_in_its_own_arithmetic_mode():
+    """enerf_train_step_args.mlp_precision (here 0: the fp32 MFMA kernels, one launch per net) is the mode of the step's own
+    MLP launches, handed to them as an argument: the one-call steps equal the Python-driven ones, which set the mode around
+    their launches, and the process's enerf_mlp32_precision reads the same before and after every one-call step."""
+    from enerf_amd import _lib as L
+    from enerf_amd.network import NeRFNetwork
+    from enerf_amd.trainer import TrainHarness
+    data = _batches(4, 1024, 2)
+    modes = []
+
+    def around(orig, *a, **k):
+        before = L.lib().enerf_mlp32_precision(-1)
+        out = orig(*a, **k)
+        modes.append((before, L.lib().enerf_mlp32_precision(-1)))
+        return out
+
+    runs = []
+    for native in (True, False):
+        torch.manual_seed(0)
+        model = NeRFNetwork(encoding="hashgrid", bound=2, cuda_ray=True, out_dim_color=3).to(DEV)
+        model.mlp_precision = 0
+        h = TrainHarness(model, lr=1e-2, occupancy="synthetic")
+        h.native_step = native
+        runs.append(_seven_steps(model, h, data, around))
+    (la, ca), (lb, cb) = runs
+    assert len(modes) == 6 and all(before == after == modes[0][0] != 0 for before, after in modes), modes
+    assert torch.equal(ca, cb)
+    assert np.abs(la - lb).max() <= 1e-5 * np.abs(lb).max(), (la, lb)
+
+
 def test_one_call_step_refused_in_the_middle_leaves_nothing_armed():
-    """enerf_train_step_mse arms one-shot requests in the library's other files (valid-row counts, the MLP precision, the
-    side stream's signal ...).  A step that is refused half-way -- here the next batch's march with max_steps = 0, which
-    enerf_march_rays_train_ex rejects by argument validation, after the forward and the MLP backward have been issued with the
-    step's rows armed -- must leave none of them behind: the Python-driven steps that follow on the same model see the same
-    samples and losses as on a model that never made the failing call."""
+    """enerf_train_step_mse takes what modifies its MLP launches (valid-row counts, the arithmetic mode, the side stream's
+    signal, the two nets' shared reduce launch) as arguments of the library's internal entry points, and disarms the march
+    one-shots its caller may have armed on the way out.  A step that is refused half-way -- here the next batch's march with
+    max_steps = 0, which enerf_march_rays_train_ex rejects by argument validation, after the forward and the MLP backward
+    have been issued on the step's rows -- must leave nothing behind: the Python-driven steps that follow on the same model
+    see the same samples and losses as on a model that never made the failing call."""
     import ctypes
     from enerf_amd import _lib as L
     from enerf_amd.network import NeRFNetwork
