@@ -212,10 +212,11 @@ struct CarriedMarch {
 };
 // raymarching.hip: march_rays_train_ex(...) split around a carrying launch, near / far computed inside the count pass from
 // nf_aabb / nf_min_near (enerf_march_fuse_near_far's arguments).  begin: 0 = *job is the call's count pass (the workspace
-// is prepared) and *march its scan + write; 1 = this call cannot be served that way (another marcher, a count mirror armed,
-// a kept counter ...): make the ordinary call; < 0 = error.  end: scan + write of the n marches on `s` (behind the launch
-// that carried the jobs), in order.  Two marches may be pending at a time, each with a chunk log of its own: `ws_slot` is
-// WS_MARCH or WS_MARCH2.  `share`: how many marches will ride in the launch (splits the workgroups).
+// is prepared) and *march its scan + write; 1 = this call cannot be served that way (another marcher, a kept counter ...):
+// make the ordinary call; < 0 = error.  The carried form stores no count mirror: whether one is wanted is the caller's
+// knowledge, who then makes the ordinary call.  end: scan + write of the n marches on `s` (behind the launch that carried
+// the jobs), in order.  Two marches may be pending at a time, each with a chunk log of its own: `ws_slot` is WS_MARCH or
+// WS_MARCH2.  `share`: how many marches will ride in the launch (splits the workgroups).
 int march_carry_begin(const float* rays_o, const float* rays_d, const uint8_t* grid, float bound, float dt_gamma,
                       uint32_t max_steps, uint32_t N, uint32_t C, uint32_t H, uint32_t M, const float* nears,
                       const float* fars, float* xyzs, float* dirs, float* deltas, int32_t* rays, int32_t* counter,
@@ -223,11 +224,12 @@ int march_carry_begin(const float* rays_o, const float* rays_d, const uint8_t* g
                       MarchCountJob* job, CarriedMarch* march, uint32_t share = 1);
 int march_carry_end(const CarriedMarch* marches, uint32_t n, hipStream_t s);
 int march_carry_count_now(const MarchCountJob* job, hipStream_t s);     // (the carrying launch did not take the job)
-// raymarching.hip: enerf_march_rays_train_ex with the near / far request as arguments (a count mirror armed is still taken)
+// raymarching.hip: enerf_march_rays_train_ex with the near / far request and the count mirror (enerf_march_mirror_count's
+// host pointer, or nullptr) as arguments: the process's one-shot requests are neither read nor cleared
 int march_rays_train(const float* rays_o, const float* rays_d, const uint8_t* grid, float bound, float dt_gamma,
                      uint32_t max_steps, uint32_t N, uint32_t C, uint32_t H, uint32_t M, const float* nears,
                      const float* fars, float* xyzs, float* dirs, float* deltas, int32_t* rays, int32_t* counter,
-                     uint32_t perturb, uint32_t zero_unwritten, const float* nf_aabb, float nf_min_near,
+                     uint32_t perturb, uint32_t zero_unwritten, const float* nf_aabb, float nf_min_near, int32_t* count_host,
                      enerf_stream_t stream);
 
 // ---- wave-level primitives (wave64) ----------------------------------------

@@ -1262,10 +1262,11 @@ static inline size_t march_log_bytes(uint32_t N, uint32_t H) {
 static const float* g_nf_aabb = nullptr;
 static float g_nf_min_near = 0.0f;
 static int32_t* g_count_mirror = nullptr;      // enerf_march_mirror_count (armed for one count pass)
-// Both are one-shot requests for "the next march".  Every public march entry point takes them -- consumes AND disarms --
-// as its first statement, before any early return (N == 0, bad arguments, a workspace failure), so that a request can never
-// outlive the call it was made for and reach an unrelated march with a stale aabb / host pointer.  The whole-step entry
-// points disarm again on their way out (train_step.hip: ~Step) in case a request was armed for a march they never reached.
+// Both are one-shot requests for "the next PUBLIC march".  enerf_march_rays_train_ex and enerf_march_rays_train_count take
+// them -- consume AND disarm -- as their first statement, before any early return (N == 0, bad arguments, a workspace
+// failure), so that a request can never outlive the call it was made for and reach an unrelated march with a stale aabb /
+// host pointer, and hand the values on as arguments.  Nothing else reads them: the library's own marches (train_step.hip)
+// go through enerf::march_rays_train / march_carry_begin with values of their own.
 struct MarchOneShot {
     const float* nf_aabb;
     float nf_min_near;
@@ -1285,11 +1286,9 @@ static int march_train_count(const float* rays_o, const float* rays_d, const uin
                              bool use_box, bool fresh_counter, const MarchOneShot& once, hipStream_t s,
                              MarchCountJob* carry_job = nullptr, int ws_slot = WS_MARCH) {
     if (int e = workspace_family_enter(0, s)) return e;
-    const float* nf_aabb = once.nf_aabb;
-    const float g_nf_min_near = once.nf_min_near;
-    int32_t* mirror = once.mirror;
+    const float* nf_aabb = once.nf_aabb;      // (taken out of the count pass below where near / far get a launch of their own)
     if (nf_aabb && !(march_uses_lattice(dt_gamma, max_steps, C, H) && !march_uses_threads(N, H))) {
-        k_near_far<<<div_up(N, 256), 256, 0, s>>>(rays_o, rays_d, nf_aabb, N, g_nf_min_near, (float*)nears, (float*)fars);
+        k_near_far<<<div_up(N, 256), 256, 0, s>>>(rays_o, rays_d, nf_aabb, N, once.nf_min_near, (float*)nears, (float*)fars);
         nf_aabb = nullptr;
     }
     if (march_uses_lattice(dt_gamma, max_steps, C, H)) {
@@ -1328,7 +1327,7 @@ static int march_train_count(const float* rays_o, const float* rays_d, const uin
         else
         {
             MarchCountJob job = {rays_o, rays_d, grid, bound, max_steps, N, C, H, nears, fars, rays, perturb, log, nlog,
-                                 occ_keys, nf_aabb, g_nf_min_near, (float*)nears, (float*)fars,
+                                 occ_keys, nf_aabb, once.nf_min_near, (float*)nears, (float*)fars,
                                  background ? min(div_up(N, 4), count_blocks) : div_up(N, 4)};
             if (carry_job) {
                 // (enerf::march_carry_begin: the count pass rides in another launch; nothing else of this function runs)
@@ -1342,7 +1341,7 @@ static int march_train_count(const float* rays_o, const float* rays_d, const uin
                                                    fars, rays, perturb);
     }
     if (N <= 16384u) {
-        k_march_scan<<<1, 1024, 0, s>>>(rays, counter, N, fresh_counter ? 1u : 0u, mirror);
+        k_march_scan<<<1, 1024, 0, s>>>(rays, counter, N, fresh_counter ? 1u : 0u, once.mirror);
     } else {
         const uint32_t ntiles = div_up(N, 1024);
         uint32_t* tiles = (uint32_t*)workspace(WS_SCAN, (size_t)ntiles * sizeof(uint32_t));
@@ -1350,7 +1349,7 @@ static int march_train_count(const float* rays_o, const float* rays_d, const uin
         k_march_scan_tile_sums<<<ntiles, 1024, 0, s>>>(rays, N, tiles);
         k_march_scan_tiles<<<1, 1024, 0, s>>>(tiles, ntiles, counter, N, fresh_counter ? 1u : 0u);
         k_march_scan_apply<<<ntiles, 1024, 0, s>>>(rays, N, tiles);
-        if (mirror && hipMemcpyAsync(mirror, counter, 2 * sizeof(int32_t), hipMemcpyDeviceToHost, s) != hipSuccess)
+        if (once.mirror && hipMemcpyAsync(once.mirror, counter, 2 * sizeof(int32_t), hipMemcpyDeviceToHost, s) != hipSuccess)
             ENERF_BADARG("march_rays_train: could not mirror the counter to the host");      // (large batches: a copy)
     }
     return 0;
@@ -1405,9 +1404,9 @@ int enerf_march_rays_train_ex(const float* rays_o, const float* rays_d, const ui
                               const float* nears, const float* fars, float* xyzs, float* dirs, float* deltas,
                               int32_t* rays, int32_t* counter, uint32_t perturb, uint32_t zero_unwritten,
                               enerf_stream_t stream) {
-    // (the near / far request as arguments; the callee takes -- disarms -- both one-shots)
+    const MarchOneShot once = march_take_oneshot();
     return enerf::march_rays_train(rays_o, rays_d, grid, bound, dt_gamma, max_steps, N, C, H, M, nears, fars, xyzs, dirs, deltas,
-                                   rays, counter, perturb, zero_unwritten, g_nf_aabb, g_nf_min_near, stream);
+                                   rays, counter, perturb, zero_unwritten, once.nf_aabb, once.nf_min_near, once.mirror, stream);
 }
 
 }  // extern "C"
@@ -1416,8 +1415,8 @@ int enerf::march_rays_train(const float* rays_o, const float* rays_d, const uint
                             uint32_t max_steps, uint32_t N, uint32_t C, uint32_t H, uint32_t M, const float* nears,
                             const float* fars, float* xyzs, float* dirs, float* deltas, int32_t* rays, int32_t* counter,
                             uint32_t perturb, uint32_t zero_unwritten, const float* nf_aabb, float nf_min_near,
-                            enerf_stream_t stream) {
-    const MarchOneShot once = {nf_aabb, nf_min_near, march_take_oneshot().mirror};
+                            int32_t* count_host, enerf_stream_t stream) {
+    const MarchOneShot once = {nf_aabb, nf_min_near, count_host};
     if (N == 0) {
         if (zero_unwritten && M) {
             (void)hipMemsetAsync(xyzs, 0, (size_t)M * 12, (hipStream_t)stream);
@@ -1744,8 +1743,8 @@ int enerf::march_carry_begin(const float* rays_o, const float* rays_d, const uin
                              uint32_t perturb, uint32_t flags, const float* nf_aabb, float nf_min_near, hipStream_t s,
                              int ws_slot, MarchCountJob* job, CarriedMarch* march, uint32_t share) {
     // what the carried form serves: the wave-per-ray lattice marcher, one-launch scan sizes, a counter taken as (0, 0)
-    // (flags bit 3), no count mirror waiting (the cold window's host watches for k_march_scan's store)
-    if (N == 0 || N > 16384u || C == 0 || H < 2 || max_steps == 0 || !(flags & 8u) || g_count_mirror != nullptr ||
+    // (flags bit 3).  It has no mirror store: a caller that wants its count mirrored makes the ordinary call.
+    if (N == 0 || N > 16384u || C == 0 || H < 2 || max_steps == 0 || !(flags & 8u) ||
         !march_uses_lattice(dt_gamma, max_steps, C, H) || march_uses_threads(N, H))
         return 1;
     if (ws_slot != WS_MARCH && ws_slot != WS_MARCH2) ENERF_BADARG("march_carry_begin: the chunk log is WS_MARCH or WS_MARCH2");

@@ -18,8 +18,10 @@
 // waits for (marches_side), or without a second stream: its count pass rides in the optimizer's launch, scan + write follow
 // it (marches_begin, optimizer).  What rides in another kernel's launch -- the fragments' build, the weight-gradient sums,
 // the count passes -- and what modifies an MLP launch -- the rows that count, the arithmetic mode, the completion signal, the
-// two nets' shared reduce launch -- is an argument of that launch's internal entry point (common.h) and a local value here:
-// the step neither reads nor changes the process's enerf_mlp32_* settings, bar the arithmetic mode where mlp_precision < 0.
+// two nets' shared reduce launch -- is an argument of that launch's internal entry point (common.h) and a local value here;
+// so are the next march's near / far request and count mirror (next_count_host).  The step neither reads nor changes the
+// process's enerf_mlp32_* settings, bar the arithmetic mode where mlp_precision < 0, nor the public marches' one-shot requests
+// (enerf_march_fuse_near_far, enerf_march_mirror_count).  Where its next marches ran it says in the struct's `report`.
 #include <hip/hip_runtime.h>
 
 #include <chrono>
@@ -73,14 +75,6 @@ public:
             t_prev_ = std::chrono::steady_clock::now();
         }
     }
-    Step(const Step&) = delete;
-    Step& operator=(const Step&) = delete;
-    ~Step() {
-        // (the one-shot march requests the caller may have armed for this step's own march never outlive it --
-        //  csrc/raymarching.hip: MarchOneShot)
-        enerf_march_fuse_near_far(nullptr, 0.0f);
-        enerf_march_mirror_count(nullptr);
-    }
 
     // Every timed call of the step passes its result through here: the host time since the previous one goes to the call's
     // slot (enerf_debug_step_timing).  A call that stands for `slots` calls of the unfused route occupies as many; 0: the time
@@ -110,10 +104,11 @@ struct Batch {
     float *feats, *h32, *fb_s, *fb_c, *sigma, *rgb, *g_sigmas, *g_rgbs, *dx32, *dfeat;
     uint32_t overwrite;                    // weight gradients: 1 written, 0 added to what is there
 };
-template <class R>                         // (enerf_train_step_args and enerf_step_render name these fields alike)
-Batch batch_of(const R& r, uint32_t total, uint32_t overwrite) {
-    return {r.M,    total,  r.counter, 0,     0,          r.xyzs,   r.dirs, r.feats, r.h32,
-            r.fb_s, r.fb_c, r.sigma,   r.rgb, r.g_sigmas, r.g_rgbs, r.dx32, r.dfeat, overwrite};
+// (enerf_train_step_args and enerf_step_render name these fields alike; flags: the call's, for ENERF_STEP_EVERY_ROW)
+template <class R>
+Batch batch_of(const R& r, uint32_t total, uint32_t overwrite, uint32_t flags) {
+    return {r.M,    total,  (flags & ENERF_STEP_EVERY_ROW) ? nullptr : r.counter, 0, 0, r.xyzs, r.dirs, r.feats, r.h32,
+            r.fb_s, r.fb_c, r.sigma, r.rgb, r.g_sigmas, r.g_rgbs, r.dx32, r.dfeat, overwrite};
 }
 
 struct NextMarch {
@@ -121,12 +116,13 @@ struct NextMarch {
     uint32_t N, M;
     float *nears, *fars, *xyzs, *dirs, *deltas;
     int32_t *rays, *counter;
+    int32_t* count_host;                   // the counter's mirror in pinned host memory (next_count_host), or nullptr
 };
 template <class R>
-uint32_t add_next(const R& r, NextMarch* list, uint32_t n) {
+uint32_t add_next(const R& r, NextMarch* list, uint32_t n, int32_t* count_host = nullptr) {
     if (!r.next_rays_o) return n;
-    list[n] = {r.next_rays_o, r.next_rays_d, r.next_N,      r.next_M,    r.next_nears,  r.next_fars,
-               r.next_xyzs,   r.next_dirs,   r.next_deltas, r.next_rays, r.next_counter};
+    list[n] = {r.next_rays_o, r.next_rays_d, r.next_N,      r.next_M,    r.next_nears,   r.next_fars,
+               r.next_xyzs,   r.next_dirs,   r.next_deltas, r.next_rays, r.next_counter, count_host};
     return n + 1;
 }
 
@@ -191,6 +187,8 @@ int backward(Step& st, const A* a, const Batch& b, bool signal, bool fold) {
 template <class A>
 int marches_begin(Step& st, const A* a, const NextMarch* next, uint32_t n, bool carry) {
     if (!carry || !g_carry_count || (a->march_flags & 16u)) return 0;
+    for (uint32_t q = 0; q < n; q++)
+        if (next[q].count_host) return 0;  // (the carried scan + write has no mirror store)
     for (uint32_t q = 0; q < n; q++) {
         const NextMarch& m = next[q];
         // (near / far inside the count pass; the second pending march logs into a workspace of its own)
@@ -217,7 +215,7 @@ int marches_side(Step& st, const A* a, const NextMarch* next, uint32_t n) {
         // (near / far inside the march's count pass: one launch less at the head of the chain the next step waits for)
         if (int rc = st.run(march_rays_train(m.rays_o, m.rays_d, a->bitfield, a->bound, a->dt_gamma, a->max_steps, m.N,
                                              a->cascade, a->grid_size, m.M, m.nears, m.fars, m.xyzs, m.dirs, m.deltas, m.rays,
-                                             m.counter, a->perturb, a->march_flags, a->aabb, a->min_near, ss)))
+                                             m.counter, a->perturb, a->march_flags, a->aabb, a->min_near, m.count_host, ss)))
             return rc;
     }
     return 0;
@@ -234,7 +232,7 @@ int table_backward(Step& st, const A* a, const Batch& b, uint32_t defer) {
 // Table Adam from the records + the MLP weights' Adam, with what the step hands the launch (weight-gradient sums, count
 // passes), and the carried marches' scan + write behind it
 template <class A>
-int optimizer(Step& st, const A* a, const char* who) {
+int optimizer(Step& st, A* a, const char* who) {
     enerf_stream_t s = a->stream;
     uint32_t taken = 0;
     if (int rc = st.run(grid_adam_from_records(a->table, a->table_grad, a->table_m, a->table_v, a->offsets, 16, 2, a->lr, a->beta1,
@@ -251,6 +249,7 @@ int optimizer(Step& st, const A* a, const char* who) {
             if (int rc = st.run(march_carry_count_now(&st.count_jobs[q], (hipStream_t)s))) return rc;
     if (int rc = st.run(march_carry_end(st.marches, st.counts, (hipStream_t)s))) return rc;
     g_carried_steps++;
+    a->report |= ENERF_STEP_MARCH_CARRIED;
     return 0;
 }
 
@@ -274,18 +273,19 @@ int event_loss(const enerf_event_step_args* a) {
 
 }  // namespace
 
-extern "C" int enerf_train_step_mse(const enerf_train_step_args* a) {
+extern "C" int enerf_train_step_mse(enerf_train_step_args* a) {
     if (!a) ENERF_BADARG("train_step_mse: null arguments");
     if (a->struct_bytes != sizeof(enerf_train_step_args))
         ENERF_BADARG("train_step_mse: struct of %u bytes, this library expects %zu", a->struct_bytes,
                      sizeof(enerf_train_step_args));
+    a->report = 0;
     if (a->M == 0 || a->N == 0) return 0;
     Step st(a, g_host_timing);
     // flags bit 0, data parallel: the gradient has to exist to be averaged -- no optimizer here, so nothing rides in its launch
     const bool dp = (a->flags & 1u) != 0;
-    const Batch b = batch_of(*a, a->M, 1);
+    const Batch b = batch_of(*a, a->M, 1, a->flags);
     NextMarch next[1];
-    const uint32_t n_next = add_next(*a, next, 0);
+    const uint32_t n_next = add_next(*a, next, 0, a->next_count_host);
     if (int rc = forward(st, a, b, true, 0)) return rc;
     // compositing forward + loss gradient + compositing backward
     if (int rc = st.run(enerf_composite_rays_train_fwd_bwd_mse(a->sigma, a->rgb, a->deltas, a->rays, a->M, a->N, a->weights_sum,
@@ -307,7 +307,7 @@ extern "C" int enerf_train_step_mse(const enerf_train_step_args* a) {
 
 // The event-only step with both renders' samples as ONE batch of 2 M rows (enerf_event_step_args.flags bit 1): compositing
 // stays per render, on the halves.  Real rows: the first render's M + min(counter_2, M).
-static int train_step_events_merged(const enerf_event_step_args* a) {
+static int train_step_events_merged(enerf_event_step_args* a) {
     const enerf_step_render &r0 = a->r[0], &r1 = a->r[1];
     const uint32_t M = r0.M, M2 = 2 * M;
     if (r1.M != M || r1.xyzs != r0.xyzs + (size_t)3 * M || r1.dirs != r0.dirs + (size_t)3 * M ||
@@ -316,7 +316,7 @@ static int train_step_events_merged(const enerf_event_step_args* a) {
     if (!a->m_feats || !a->m_h32 || !a->m_sigma || !a->m_rgb || !a->m_g_sigmas || !a->m_g_rgbs || !a->m_dx32 || !a->m_dfeat)
         ENERF_BADARG("train_step_events(merged): the m_* scratch buffers are required");
     Step st(a, false);
-    const bool skip = r0.counter != nullptr && r1.counter != nullptr;
+    const bool skip = !(a->flags & ENERF_STEP_EVERY_ROW) && r0.counter != nullptr && r1.counter != nullptr;
     const Batch b = {M2,         M2,      skip ? r1.counter : nullptr, M, M, r0.xyzs, r0.dirs, a->m_feats, a->m_h32, a->m_fb_s,
                      a->m_fb_c,  a->m_sigma, a->m_rgb, a->m_g_sigmas, a->m_g_rgbs, a->m_dx32, a->m_dfeat, 1};
     NextMarch next[2];
@@ -341,18 +341,19 @@ static int train_step_events_merged(const enerf_event_step_args* a) {
 // The event-only step (two renders, one loss, one optimizer pass): events.train_step_events_manual +
 // FusedAdam.step_grid_table, call for call.  Render by render, nothing rides in another launch: no fragments, weight-gradient
 // sums or marches are carried; the second render finds the first's fragments and adds its weight gradients to the first's.
-extern "C" int enerf_train_step_events(const enerf_event_step_args* a) {
+extern "C" int enerf_train_step_events(enerf_event_step_args* a) {
     if (!a) ENERF_BADARG("train_step_events: null arguments");
     if (a->struct_bytes != sizeof(enerf_event_step_args))
         ENERF_BADARG("train_step_events: struct of %u bytes, this library expects %zu", a->struct_bytes,
                      sizeof(enerf_event_step_args));
+    a->report = 0;
     if (a->r[0].N == 0 || a->r[0].N != a->r[1].N || a->r[0].M == 0 || a->r[1].M == 0)
         ENERF_BADARG("train_step_events: both renders take the same (non-zero) number of rays and a sample budget");
     if (!a->bg_color || !a->pols) ENERF_BADARG("train_step_events: bg_color and pols are required");
     if (a->flags & 2u) return train_step_events_merged(a);
     Step st(a, false);
     const uint32_t total = a->r[0].M + a->r[1].M;
-    const Batch b[2] = {batch_of(a->r[0], total, 1), batch_of(a->r[1], total, 0)};
+    const Batch b[2] = {batch_of(a->r[0], total, 1, a->flags), batch_of(a->r[1], total, 0, a->flags)};
     NextMarch next[2];
     const uint32_t n_next = add_next(a->r[1], next, add_next(a->r[0], next, 0));
     for (uint32_t k = 0; k < 2; k++) {

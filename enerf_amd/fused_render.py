@@ -75,6 +75,41 @@ class _Stage(dict):
                 pass
 
 
+def _budget_rows(count):
+    """A sample count rounded as the reference rounds its budget (raymarching.py:186-189, align = 128)."""
+    return count + (128 - count % 128)
+
+
+def _cold_crop(model, m, N, max_steps):
+    """The reference's crop of its N * max_steps rows to a count of m samples; remembered on the model, for the cold
+    window's later reservations."""
+    rows = model._cold_rows = min(_budget_rows(m), N * int(max_steps))
+    return rows
+
+
+def _ray_bufs(N, dev):
+    """What a march of N rays fills per ray."""
+    return dict(nears=torch.empty(N, dtype=torch.float32, device=dev), fars=torch.empty(N, dtype=torch.float32, device=dev),
+                rays=torch.empty(N, 3, dtype=torch.int32, device=dev))
+
+
+def _sample_bufs(rows, dev):
+    """One set of sample buffers of `rows` rows, uninitialised: the write pass zero-fills the rows no ray writes."""
+    f32 = dict(dtype=torch.float32, device=dev)
+    return dict(xyzs=torch.empty(rows, 3, **f32), dirs=torch.empty(rows, 3, **f32), deltas=torch.empty(rows, 2, **f32))
+
+
+def _write_pass(model, pre, rays_o, rays_d, perturb, dt_gamma, max_steps, rows):
+    """The write pass of the stage `pre`, whose count pass has run, into fresh buffers of `rows` rows -> the stage."""
+    bufs = _sample_bufs(rows, rays_o.device)
+    _rb.march_rays_train_write(rays_o, rays_d, model._buffers["density_bitfield"], model.bound, float(dt_gamma),
+                               int(max_steps), rays_o.shape[0], model.cascade, model.grid_size, rows, pre["nears"],
+                               pre["fars"], bufs["xyzs"], bufs["dirs"], bufs["deltas"], pre["rays"], pre["counter"],
+                               bool(perturb), 1)
+    pre.update(bufs, M=rows)
+    return pre
+
+
 def march_stage(model, rays_o, rays_d, counter, mean_count, perturb, force_all_rays, dt_gamma, max_steps,
                 background=False, defer=False, launch_stream=None, after_signal=False):
     """near_far_from_aabb + march_rays_train: everything of a training render that does not read the parameters.
@@ -98,29 +133,22 @@ def march_stage(model, rays_o, rays_d, counter, mean_count, perturb, force_all_r
     N = rays_o.shape[0]
     dev = rays_o.device
     budgeted = not (force_all_rays or mean_count <= 0)
-    nears = torch.empty(N, dtype=torch.float32, device=dev)
-    fars = torch.empty(N, dtype=torch.float32, device=dev)
-    rays = torch.empty(N, 3, dtype=torch.int32, device=dev)
-    if budgeted:
-        M = mean_count + (128 - mean_count % 128)            # raymarching.py:186-189 (align = 128)
-        # budgeted buffers: the write pass zero-fills the rows no ray writes, so no torch.zeros passes over them
-        xyzs = torch.empty(M, 3, dtype=torch.float32, device=dev)
-        dirs = torch.empty(M, 3, dtype=torch.float32, device=dev)
-        deltas = torch.empty(M, 2, dtype=torch.float32, device=dev)
+    pre = _Stage(_ray_bufs(N, dev), counter=counter)
+    nears, fars, rays = pre["nears"], pre["fars"], pre["rays"]
     spec_rows = 0
+    if budgeted:
+        M = _budget_rows(mean_count)
+        samples = _sample_bufs(M, dev)           # (the write pass zero-fills the rows no ray writes)
     if not budgeted and defer and not force_all_rays:
         # no budget yet, but the previous render's count is known: its rows + 1/8 are reserved here and the write pass
         # follows the count pass on the same stream, unseen by the host; finish_march() keeps the result when the count
         # it reads back fits (consecutive batches differ by a few per cent) and repeats the write pass when not
         last = int(getattr(model, "_cold_rows", 0))
         if last > 0:
-            spec_rows = min(last + last // 8 + (128 - (last + last // 8) % 128), N * max_steps)
-            xyzs = torch.empty(spec_rows, 3, dtype=torch.float32, device=dev)
-            dirs = torch.empty(spec_rows, 3, dtype=torch.float32, device=dev)
-            deltas = torch.empty(spec_rows, 2, dtype=torch.float32, device=dev)
+            spec_rows = min(_budget_rows(last + last // 8), N * max_steps)
+            samples = _sample_bufs(spec_rows, dev)
     bufs = model._buffers                            # (nn.Module.__getattr__ is a slow path)
     bitfield = bufs["density_bitfield"]
-    pre = _Stage(nears=nears, fars=fars, rays=rays, counter=counter)
     box = occupied_box_flag(model)
     if launch_stream is not None:
         if after_signal == "ordered":
@@ -144,14 +172,14 @@ def march_stage(model, rays_o, rays_d, counter, mean_count, perturb, force_all_r
             pre["pending"] = (done, total, rays_o, rays_d, perturb, dt_gamma, max_steps)
             if spec_rows:
                 _rb.march_rays_train_write(rays_o, rays_d, bitfield, model.bound, dt_gamma, max_steps, N, model.cascade,
-                                           model.grid_size, spec_rows, nears, fars, xyzs, dirs, deltas, rays, counter,
-                                           perturb, 1)
-                pre["speculative"] = (spec_rows, xyzs, dirs, deltas)
+                                           model.grid_size, spec_rows, nears, fars, samples["xyzs"], samples["dirs"],
+                                           samples["deltas"], rays, counter, perturb, 1)
+                pre["speculative"] = (spec_rows, samples["xyzs"], samples["dirs"], samples["deltas"])
         else:
             _rb.march_rays_train_ex(rays_o, rays_d, bitfield, model.bound, dt_gamma, max_steps, N,
-                                    model.cascade, model.grid_size, M, nears, fars, xyzs, dirs, deltas, rays, counter,
-                                    perturb, box | (3 if background else 1) | 8)
-            pre.update(xyzs=xyzs, dirs=dirs, deltas=deltas, M=M)
+                                    model.cascade, model.grid_size, M, nears, fars, samples["xyzs"], samples["dirs"],
+                                    samples["deltas"], rays, counter, perturb, box | (3 if background else 1) | 8)
+            pre.update(samples, M=M)
         if launch_stream is not None:
             pre["ready"] = torch.cuda.Event()
             pre["ready"].record(launch_stream)
@@ -170,34 +198,22 @@ def finish_march(model, pre):
     done, total, rays_o, rays_d, perturb, dt_gamma, max_steps = pending
     done.synchronize()
     N = rays_o.shape[0]
-    dev = rays_o.device
     m = int(total[0])
-    M = min(m + (128 - m % 128), N * max_steps)              # the reference's crop of its N * max_steps buffers
-    model._cold_rows = M
+    M = _cold_crop(model, m, N, max_steps)
     spec = pre.pop("speculative", None)
     if spec is not None and M <= spec[0] and m < N * max_steps:
         # the write pass already ran behind the count pass into buffers at least this large: the rows are the same
         # (nothing is dropped below N * max_steps samples, rows past the count are zero-filled either way)
         pre.update(xyzs=spec[1][:M], dirs=spec[2][:M], deltas=spec[3][:M], M=M)
         return pre
-    xyzs = torch.empty(M, 3, dtype=torch.float32, device=dev)
-    dirs = torch.empty(M, 3, dtype=torch.float32, device=dev)
-    deltas = torch.empty(M, 2, dtype=torch.float32, device=dev)
-    _rb.march_rays_train_write(rays_o, rays_d, model._buffers["density_bitfield"], model.bound, dt_gamma, max_steps, N,
-                               model.cascade, model.grid_size, M, pre["nears"], pre["fars"], xyzs, dirs, deltas,
-                               pre["rays"], pre["counter"], perturb, 1)
-    pre.update(xyzs=xyzs, dirs=dirs, deltas=deltas, M=M)
-    return pre
+    return _write_pass(model, pre, rays_o, rays_d, perturb, dt_gamma, max_steps, M)
 
 
 class _FusedRenderTrain(Function):
     @staticmethod
-    def forward(ctx, rays_o, rays_d, model, bg_color, counter, mean_count, perturb, force_all_rays, dt_gamma,
-                max_steps, pre, embeddings, *weights):
+    def forward(ctx, rays_o, model, bg_color, pre, embeddings, *weights):
         N = rays_o.shape[0]
         dev = rays_o.device
-        if pre is None:
-            pre = march_stage(model, rays_o, rays_d, counter, mean_count, perturb, force_all_rays, dt_gamma, max_steps)
         nears, fars, xyzs, dirs, deltas, rays, M = (pre[k] for k in ("nears", "fars", "xyzs", "dirs", "deltas", "rays",
                                                                      "M"))
 
@@ -232,7 +248,7 @@ class _FusedRenderTrain(Function):
         _rb.composite_rays_train_backward(g_ws, g_image, sigmas, rgb, deltas, rays, weights_sum, image, M, N, g_sigmas,
                                           g_rgbs)
         g = fnet.nerf_backward(ctx.sv, g_sigmas, g_rgbs, sigma_scale=scale)
-        return (None,) * 11 + g
+        return (None,) * 4 + g
 
 
 def _budget(model):
@@ -255,6 +271,14 @@ def _next_counter(model):
         counter = model._buffers["step_counter"][model.last_counter_slot]
         model.local_step += 1
     return counter
+
+
+def _pinned_ring(model):
+    """The pinned host copy of the step-counter ring (made on first use)."""
+    host = getattr(model, "_ring_host", None)
+    if host is None:
+        host = model._ring_host = torch.empty(16, 2, dtype=torch.int32, pin_memory=True)
+    return host
 
 
 def early_mean_count(model):
@@ -283,9 +307,7 @@ def early_mean_count(model):
     if last is None or stash:                      # the last march ran on the training stream / an unconsumed stage
         return None
     _ready, stream = last
-    host = getattr(model, "_ring_host", None)
-    if host is None:
-        host = model._ring_host = torch.empty(16, 2, dtype=torch.int32, pin_memory=True)
+    host = _pinned_ring(model)
     with torch.cuda.stream(stream):
         host.copy_(model._buffers["step_counter"], non_blocking=True)
         done = torch.cuda.Event()
@@ -300,9 +322,7 @@ def stage_ring_copy(model):
     stream itself (the one-call step carries the next batch's march in its optimizer launch: csrc/train_step.hip), early_mean_count
     has no side stream to read the ring behind: TrainHarness calls this in front of the window's LAST step -- which marches
     nothing, the update that follows voids any stage -- so that the copy is complete a whole step before the update needs it."""
-    host = getattr(model, "_ring_host", None)
-    if host is None:
-        host = model._ring_host = torch.empty(16, 2, dtype=torch.int32, pin_memory=True)
+    host = _pinned_ring(model)
     host.copy_(model._buffers["step_counter"], non_blocking=True)
     done = torch.cuda.Event()
     done.record()
@@ -323,11 +343,8 @@ def prefetch_march(model, rays_o, rays_d, perturb=True, dt_gamma=0, max_steps=10
     MFMA- and HBM-bound backward kernels.  The consumer waits on the stage's event."""
     rays_o = rays_o.contiguous().view(-1, 3)
     rays_d = rays_d.contiguous().view(-1, 3)
-    key = (rays_o.data_ptr(), rays_d.data_ptr(), rays_o.shape[0], bool(perturb), float(dt_gamma), int(max_steps))
-    stash = getattr(model, "_premarched", None)
-    if not isinstance(stash, dict):
-        stash = model._premarched = {}
-    if any("pending" in p for p in stash.values()):
+    stash = _stash_if_free(model)
+    if stash is None:
         # an unbudgeted stage is waiting for its write pass, and the marcher's chunk log (count -> write) is one
         # per-process buffer: a second count now would overwrite it.  The second render of an event step marches inline.
         return
@@ -339,7 +356,7 @@ def prefetch_march(model, rays_o, rays_d, perturb=True, dt_gamma=0, max_steps=10
                           float(dt_gamma), int(max_steps), background=background, defer=True, launch_stream=stream,
                           after_signal=after_signal)
     pre["slot"] = getattr(model, "last_counter_slot", None)
-    stash[key] = pre                                 # (an event step stashes both of its renders)
+    stash[_stage_key(rays_o, rays_d, perturb, dt_gamma, max_steps)] = pre      # (an event step stashes both of its renders)
 
 
 def premarch_count(model, rays_o, rays_d, perturb=True, dt_gamma=0, max_steps=1024):
@@ -350,57 +367,34 @@ def premarch_count(model, rays_o, rays_d, perturb=True, dt_gamma=0, max_steps=10
     has -- the same launches as march_rays_train_ex, in the same order."""
     rays_o = rays_o.contiguous().view(-1, 3)
     rays_d = rays_d.contiguous().view(-1, 3)
-    N, dev = rays_o.shape[0], rays_o.device
-    key = (rays_o.data_ptr(), rays_d.data_ptr(), N, bool(perturb), float(dt_gamma), int(max_steps))
-    nears = torch.empty(N, dtype=torch.float32, device=dev)
-    fars = torch.empty(N, dtype=torch.float32, device=dev)
-    rays = torch.empty(N, 3, dtype=torch.int32, device=dev)
+    N = rays_o.shape[0]
+    pre = _ray_bufs(N, rays_o.device)
     counter = _next_counter(model)
     bufs = model._buffers
-    _rb.near_far_from_aabb(rays_o, rays_d, bufs["aabb_train"], N, model.min_near, nears, fars)
+    _rb.near_far_from_aabb(rays_o, rays_d, bufs["aabb_train"], N, model.min_near, pre["nears"], pre["fars"])
     _rb.march_rays_train_count(rays_o, rays_d, bufs["density_bitfield"], model.bound, float(dt_gamma), int(max_steps), N,
-                               model.cascade, model.grid_size, nears, fars, rays, counter, bool(perturb),
-                               occupied_box_flag(model) | 8)
-    model._premarched = {key: dict(nears=nears, fars=fars, rays=rays, counter=counter,
-                                   counted=(rays_o, rays_d, bool(perturb), float(dt_gamma), int(max_steps)),
-                                   slot=getattr(model, "last_counter_slot", None))}
+                               model.cascade, model.grid_size, pre["nears"], pre["fars"], pre["rays"], counter,
+                               bool(perturb), occupied_box_flag(model) | 8)
+    pre.update(counter=counter, counted=(rays_o, rays_d, bool(perturb), float(dt_gamma), int(max_steps)),
+               slot=getattr(model, "last_counter_slot", None))
+    model._premarched = {_stage_key(rays_o, rays_d, perturb, dt_gamma, max_steps): pre}
 
 
 def _finish_counted(model, pre):
     """Write pass of a premarch_count stage, with the budget the host has by now (march_stage's budgeted branch)."""
     rays_o, rays_d, perturb, dt_gamma, max_steps = pre.pop("counted")
     mean_count = _budget(model)
-    N, dev = rays_o.shape[0], rays_o.device
     if mean_count <= 0:                         # no budget after all (first window): the reference's crop of N * max_steps
-        m = int(pre["counter"][0].item())
-        M = min(m + (128 - m % 128), N * max_steps)
-        model._cold_rows = M
+        M = _cold_crop(model, int(pre["counter"][0].item()), rays_o.shape[0], max_steps)
     else:
-        M = mean_count + (128 - mean_count % 128)
-    xyzs = torch.empty(M, 3, dtype=torch.float32, device=dev)
-    dirs = torch.empty(M, 3, dtype=torch.float32, device=dev)
-    deltas = torch.empty(M, 2, dtype=torch.float32, device=dev)
-    _rb.march_rays_train_write(rays_o, rays_d, model._buffers["density_bitfield"], model.bound, dt_gamma, max_steps, N,
-                               model.cascade, model.grid_size, M, pre["nears"], pre["fars"], xyzs, dirs, deltas,
-                               pre["rays"], pre["counter"], perturb, 1)
-    pre.update(xyzs=xyzs, dirs=dirs, deltas=deltas, M=M)
-    return pre
+        M = _budget_rows(mean_count)
+    return _write_pass(model, pre, rays_o, rays_d, perturb, dt_gamma, max_steps, M)
 
 
 def render_train(model, rays_o, rays_d, bg_color, perturb, force_all_rays, dt_gamma, max_steps):
     """-> depth [N], image [N,3] (+ the step counter bookkeeping of run_cuda)."""
-    pre = _take_premarched(model, rays_o, rays_d, perturb, dt_gamma, max_steps)
-    if force_all_rays:
-        pre = None
-    if pre is not None:
-        model.rendered_counter_slot = pre["slot"]
-    counter = None
-    if pre is None:
-        counter = _next_counter(model)
-        model.rendered_counter_slot = getattr(model, "last_counter_slot", None)
-    params = fnet.network_params(model)
-    return _FusedRenderTrain.apply(rays_o, rays_d, model, bg_color, counter, _budget(model), bool(perturb),
-                                   bool(force_all_rays), float(dt_gamma), int(max_steps), pre, *params)
+    pre = _take_or_march(model, rays_o, rays_d, perturb, dt_gamma, max_steps, force_all_rays=force_all_rays)
+    return _FusedRenderTrain.apply(rays_o, model, bg_color, pre, *fnet.network_params(model))
 
 
 def _check_cold_stage(model, pre, rays_o, rays_d, perturb, dt_gamma, max_steps):
@@ -429,30 +423,30 @@ def _check_cold_stage(model, pre, rays_o, rays_d, perturb, dt_gamma, max_steps):
                 model._cold_watch_failed = True
         if hv[0] < 0 or hv[1] < 0:
             done.synchronize()
-    m = int(hv[0])
-    N = rays_o.shape[0]
-    rows = min(m + (128 - m % 128), N * int(max_steps))
-    model._cold_rows = rows
+    rows = _cold_crop(model, int(hv[0]), rays_o.shape[0], max_steps)
     if rows <= cap:
         return pre
-    dev = rays_o.device
-    xyzs = torch.empty(rows, 3, dtype=torch.float32, device=dev)
-    dirs = torch.empty(rows, 3, dtype=torch.float32, device=dev)
-    deltas = torch.empty(rows, 2, dtype=torch.float32, device=dev)
-    _rb.march_rays_train_write(rays_o, rays_d, model._buffers["density_bitfield"], model.bound, float(dt_gamma),
-                               int(max_steps), N, model.cascade, model.grid_size, rows, pre["nears"], pre["fars"], xyzs,
-                               dirs, deltas, pre["rays"], pre["counter"], bool(perturb), 1)
-    out = dict(pre)
-    out.update(xyzs=xyzs, dirs=dirs, deltas=deltas, M=rows)
-    return out
+    return _write_pass(model, dict(pre), rays_o, rays_d, perturb, dt_gamma, max_steps, rows)
+
+
+def _stage_key(rays_o, rays_d, perturb, dt_gamma, max_steps):
+    return (rays_o.data_ptr(), rays_d.data_ptr(), rays_o.shape[0], bool(perturb), float(dt_gamma), int(max_steps))
+
+
+def _stash_if_free(model):
+    """The stash the next stages go into, or None while an unbudgeted stage waits there for its write pass (see
+    prefetch_march: nothing else may be marched then)."""
+    stash = getattr(model, "_premarched", None)
+    if not isinstance(stash, dict):
+        stash = model._premarched = {}
+    return None if any("pending" in p for p in stash.values()) else stash
 
 
 def _take_premarched(model, rays_o, rays_d, perturb, dt_gamma, max_steps, defer_cold_check=False):
     stash = getattr(model, "_premarched", None)
     if not stash:
         return None
-    key = (rays_o.data_ptr(), rays_d.data_ptr(), rays_o.shape[0], bool(perturb), float(dt_gamma), int(max_steps))
-    pre = stash.pop(key, None)
+    pre = stash.pop(_stage_key(rays_o, rays_d, perturb, dt_gamma, max_steps), None)
     if pre is None:
         stash.clear()                                # marched for rays that are not coming: drop, march afresh
         return None
@@ -471,8 +465,21 @@ def _take_premarched(model, rays_o, rays_d, perturb, dt_gamma, max_steps, defer_
     return finish_march(model, pre)              # unbudgeted stage: the write pass runs here, sized from the count
 
 
+def _take_or_march(model, rays_o, rays_d, perturb, dt_gamma, max_steps, defer_cold_check=False, force_all_rays=False):
+    """The batch's samples: the stage marched ahead for these rays, or a march now (always, with force_all_rays: a stage
+    marched ahead is dropped)."""
+    pre = _take_premarched(model, rays_o, rays_d, perturb, dt_gamma, max_steps, defer_cold_check=defer_cold_check)
+    if pre is not None and not force_all_rays:
+        model.rendered_counter_slot = pre["slot"]
+        return pre
+    counter = _next_counter(model)
+    model.rendered_counter_slot = getattr(model, "last_counter_slot", None)
+    return march_stage(model, rays_o, rays_d, counter, _budget(model), bool(perturb), bool(force_all_rays), float(dt_gamma),
+                       int(max_steps))
+
+
 FUSED_COMPOSITE = True        # train_step_mse: compositing forward + MSE backward as one launch
-MIRROR_COUNT = True           # cold window: the march's count goes straight to pinned host memory (enerf_march_mirror_count)
+MIRROR_COUNT = True           # cold window: the march's count goes straight to pinned host memory (next_count_host)
 import os as _os
 SKIP_PADDING_ROWS = _os.environ.get("ENERF_SKIP_PADDING_ROWS", "1") != "0"      # raw renders: the MLP kernels skip the sample budget's unfilled rows (device-side count)
 
@@ -487,14 +494,7 @@ def render_train_raw(model, rays_o, rays_d, bg_color=1, perturb=True, dt_gamma=0
     N = rays_o.shape[0]
     dev = rays_o.device
     with torch.no_grad():
-        pre = _take_premarched(model, rays_o, rays_d, perturb, dt_gamma, max_steps)
-        if pre is not None:
-            model.rendered_counter_slot = pre["slot"]
-        else:
-            counter = _next_counter(model)
-            model.rendered_counter_slot = getattr(model, "last_counter_slot", None)
-            pre = march_stage(model, rays_o, rays_d, counter, _budget(model), bool(perturb), False, float(dt_gamma),
-                              int(max_steps))
+        pre = _take_or_march(model, rays_o, rays_d, perturb, dt_gamma, max_steps)
         xyzs, dirs, deltas, rays, M = (pre[k] for k in ("xyzs", "dirs", "deltas", "rays", "M"))
         params = fnet.network_params(model)
         sigma, rgb, sv = fnet.nerf_forward(xyzs, dirs, fnet.network_cfg(model), True, params[0],
@@ -592,10 +592,11 @@ _NETS = (_fields(_vp, "embeddings", "offsets") + _fields(_f32c, "level_scale_log
          + _fields(_u32, "nh_s", "nh_c", "w0_cols_c", "out_c"))
 _NEXT_RAYS, _NEXT_SIZE = _fields(_vp, "next_rays_o", "next_rays_d"), _fields(_u32, "next_N", "next_M")
 _NEXT_OUT = _fields(_vp, *("next_" + n for n in _NEXT_BUFS))
+_EVERY_ROW, _MARCH_CARRIED = 4, 1         # ENERF_STEP_EVERY_ROW (flags), ENERF_STEP_MARCH_CARRIED (report)
 _MARCH = _fields(_vp, "aabb", "bitfield") + _fields(_f32c, "min_near", "dt_gamma")
 _MARCH_U32 = _fields(_u32, "cascade", "grid_size", "max_steps", "perturb", "march_flags")
 _OPTIM = (_fields(_vp, "table", "table_grad", "table_m", "table_v") + _fields(_f32c, "lr", "beta1", "beta2", "eps")
-          + _fields(_u32, "table_step", "n_small") + _fields(_vp, *_SMALL) + _fields(_u32, "flags", "reserved"))
+          + _fields(_u32, "table_step", "n_small") + _fields(_vp, *_SMALL) + _fields(_u32, "flags", "report"))
 
 
 def _scratch_fields(*images):             # a render's scratch: the MLP set with the image buffers where the header has them
@@ -604,7 +605,7 @@ def _scratch_fields(*images):             # a render's scratch: the MLP set with
 
 class _StepArgs(_ct.Structure):           # enerf_train_step_args
     _fields_ = (_HEAD + _SAMPLES + [("target", _vp), ("bg_scalar", _f32c), ("grad_scale", _f32c), ("loss", _vp)] + _NETS
-                + _scratch_fields() + _NEXT_RAYS + _MARCH + _NEXT_SIZE + _MARCH_U32 + _NEXT_OUT + _OPTIM)
+                + _scratch_fields() + _NEXT_RAYS + _MARCH + _NEXT_SIZE + _MARCH_U32 + _NEXT_OUT + [("next_count_host", _vp)] + _OPTIM)
 
 
 class _StepRender(_ct.Structure):         # enerf_step_render
@@ -708,12 +709,9 @@ def _mlp_scratch(rows, arch, out_c, new):
     return {name: new(name, *shape) for name, shape in shapes.items()}
 
 
-def _stage_set(Nn, Mn, f32, dev, samples=None):
+def _stage_set(Nn, Mn, dev, samples=None):
     """One set of buffers a march of Nn rays into Mn rows fills (`samples`: its xyzs / dirs / deltas, where they exist)."""
-    if samples is None:
-        samples = dict(xyzs=torch.empty(Mn, 3, **f32), dirs=torch.empty(Mn, 3, **f32), deltas=torch.empty(Mn, 2, **f32))
-    return dict(nears=torch.empty(Nn, **f32), fars=torch.empty(Nn, **f32),
-                rays=torch.empty(Nn, 3, dtype=torch.int32, device=dev), M=Mn, **samples)
+    return dict(_ray_bufs(Nn, dev), M=Mn, **(_sample_bufs(Mn, dev) if samples is None else samples))
 
 
 def _native_ctx(model, N, M, Nn, Mn, dev):
@@ -728,7 +726,7 @@ def _native_ctx(model, N, M, Nn, Mn, dev):
         setattr(a, name, buf.data_ptr())
     a.N, a.M = N, M
     a.bg_scalar, a.grad_scale = 1.0, 2.0 / (3 * N)
-    ctx.update(t=t, stages=[_stage_set(Nn, Mn, f32, dev) for _ in range(2)] if Nn else [], flip=0,
+    ctx.update(t=t, stages=[_stage_set(Nn, Mn, dev) for _ in range(2)] if Nn else [], flip=0,
                out_image=t["out_image"])
     return ctx
 
@@ -747,8 +745,7 @@ def _native_events_ctx(model, N, Ms, Nn, Mn, luma, dev):
             setattr(a, "m_" + name, buf.data_ptr())
     # the two renders' sample buffers of one stage generation are the halves of ONE allocation: a step that consumes both
     # finds the second render's rows right behind the first's M (merged layout, see train_step_events_native)
-    pairs = [dict(xyzs=torch.empty(2 * Mn, 3, **f32), dirs=torch.empty(2 * Mn, 3, **f32), deltas=torch.empty(2 * Mn, 2, **f32))
-             for _ in range(2 if Nn else 0)]
+    pairs = [_sample_bufs(2 * Mn, dev) for _ in range(2 if Nn else 0)]
     ts, stages = [], []
     for q, M in enumerate(Ms):
         def half(name, *shape):
@@ -764,7 +761,7 @@ def _native_events_ctx(model, N, Ms, Nn, Mn, luma, dev):
         a.r[q].N, a.r[q].M = N, M
         for name, buf in t.items():
             setattr(a.r[q], name, buf.data_ptr())
-        stages.append([_stage_set(Nn, Mn, f32, dev, {k: v[q * Mn:(q + 1) * Mn] for k, v in pb.items()}) for pb in pairs])
+        stages.append([_stage_set(Nn, Mn, dev, {k: v[q * Mn:(q + 1) * Mn] for k, v in pb.items()}) for pb in pairs])
     delta = torch.empty(1, N, 1 if luma else 3, **f32)
     a.delta = delta.data_ptr()
     ctx.update(t=ts, tm=tm, stages=stages, flip=[0, 0], delta=delta)
@@ -772,26 +769,6 @@ def _native_events_ctx(model, N, Ms, Nn, Mn, luma, dev):
 
 
 # ---- the per-step bookkeeping both drivers share
-def _take_or_march(model, rays_o, rays_d, perturb, dt_gamma, max_steps, defer_cold_check=False):
-    """The batch's samples: the stage marched ahead for these rays, or a march now."""
-    pre = _take_premarched(model, rays_o, rays_d, perturb, dt_gamma, max_steps, defer_cold_check=defer_cold_check)
-    if pre is not None:
-        model.rendered_counter_slot = pre["slot"]
-        return pre
-    counter = _next_counter(model)
-    model.rendered_counter_slot = getattr(model, "last_counter_slot", None)
-    return march_stage(model, rays_o, rays_d, counter, _budget(model), bool(perturb), False, float(dt_gamma), int(max_steps))
-
-
-def _stash_if_free(model):
-    """The stash the next stages go into, or None while an unbudgeted stage waits there for its write pass (see
-    prefetch_march: nothing else may be marched then)."""
-    stash = getattr(model, "_premarched", None)
-    if not isinstance(stash, dict):
-        stash = model._premarched = {}
-    return None if any("pending" in p for p in stash.values()) else stash
-
-
 def _fill_step(ctx, a):
     emb = ctx["emb"]
     if emb.grad is None:                    # the dense part of the table's gradient (levels too small to bin)
@@ -802,9 +779,14 @@ def _fill_step(ctx, a):
 
 def _fill_samples(r, pre):
     r.xyzs, r.dirs, r.deltas = pre["xyzs"].data_ptr(), pre["dirs"].data_ptr(), pre["deltas"].data_ptr()
-    r.rays = pre["rays"].data_ptr()
-    r.counter = pre["counter"].data_ptr() if SKIP_PADDING_ROWS else None
+    r.rays, r.counter = pre["rays"].data_ptr(), pre["counter"].data_ptr()
     r.next_rays_o = None
+
+
+def _step_flags(bits):
+    """The call's `flags`: with SKIP_PADDING_ROWS off the grid and MLP launches take every row of the budget (the compositing
+    needs the counter either way)."""
+    return bits if SKIP_PADDING_ROWS else bits | _EVERY_ROW
 
 
 def _fill_march(a, model, side_stream, perturb, dt_gamma, max_steps, more_flags=0):
@@ -825,10 +807,6 @@ def _next_stage(r, sets, flip, pre, counter, slot, no, nd):
     return nxt, which
 
 
-def _stage_key(no, nd, perturb, dt_gamma, max_steps):
-    return (no.data_ptr(), nd.data_ptr(), no.shape[0], bool(perturb), float(dt_gamma), int(max_steps))
-
-
 def _fill_optimizer(ctx, a, opt):
     """The optimizer block: host arrays (pointers, sizes, learning rates, step counts of the MLP weights) built once per
     context and optimizer, the scalars of this step (which advances the step counts)."""
@@ -844,12 +822,10 @@ def _fill_optimizer(ctx, a, opt):
     a.lr, a.beta1, a.beta2, a.eps, a.table_step = plan()
 
 
-def _call(entry, a, marching):
+def _call(entry, a):
     """The one call -> whether the next marches rode in its own launches, on this stream (no event to wait for then)."""
-    lib = L.lib()
-    before = lib.enerf_debug_carry_count(-2) if marching else 0
-    L.check(getattr(lib, "enerf_" + entry)(_ct.byref(a)), entry)
-    return bool(marching) and lib.enerf_debug_carry_count(-2) != before
+    L.check(getattr(L.lib(), "enerf_" + entry)(_ct.byref(a)), entry)
+    return bool(a.report & _MARCH_CARRIED)
 
 
 def _count_launches(points):
@@ -915,7 +891,7 @@ def train_step_native(model, rays_o, rays_d, target, opt, next_rays=None, side_s
                 Mn = model._cold_cap = cold_capacity(int(model._cold_rows), Nn, int(max_steps),
                                                      int(getattr(model, "_cold_cap", 0)))
             else:
-                Mn = mc + (128 - mc % 128)
+                Mn = _budget_rows(mc)
             nxt_counter = _next_counter(model)
             nxt_slot = getattr(model, "last_counter_slot", None)
 
@@ -927,7 +903,7 @@ def train_step_native(model, rays_o, rays_d, target, opt, next_rays=None, side_s
             a.target = target.contiguous().view(-1, 3).data_ptr()
             a.loss = None if loss_out is None else loss_out.data_ptr()
             # (bit 1: the sharded tail with an owner range set -- this rank's slice of the table stays as record lists)
-            a.flags = (3 if defer_dp else 1) if raw else 0
+            a.flags = _step_flags((3 if defer_dp else 1) if raw else 0)
             nxt, which = None, 0
             if stash is not None:
                 # (bit 4: this march stays on the side stream -- the cold window reads its count back behind it there)
@@ -953,16 +929,15 @@ def train_step_native(model, rays_o, rays_d, target, opt, next_rays=None, side_s
         cold_host = None
         if nxt is not None and cold_next:
             # the count of the cold window's next march travels to pinned memory (one slot per stage set): stored by the
-            # march itself (enerf_march_mirror_count) or copied behind it; what _check_cold_stage watches for is both words >= 0
+            # march itself (next_count_host) or copied behind it; what _check_cold_stage watches for is both words >= 0
             hosts = ctx.get("cold_hosts")
             if hosts is None:
                 hosts = ctx["cold_hosts"] = [torch.empty(2, dtype=torch.int32, pin_memory=True) for _ in range(2)]
             cold_host = hosts[which]
             cold_host.fill_(-1)
-            mirrored = MIRROR_COUNT
-            if mirrored:
-                L.check(L.lib().enerf_march_mirror_count(cold_host.data_ptr()), "march_mirror_count")
-        carried = _call("train_step_mse", a, nxt is not None)
+        mirrored = cold_host is not None and MIRROR_COUNT
+        a.next_count_host = cold_host.data_ptr() if mirrored else None      # (the struct is the last step's: set every time)
+        carried = _call("train_step_mse", a)
         _count_launches(M)
         if nxt is not None:
             if cold_next and not mirrored:
@@ -997,8 +972,7 @@ def train_step_events_native(model, data, loss_opt, opt, next_data=None, side_st
         if stash is not None:
             nxt_pairs = flat(next_data)
             Nn = nxt_pairs[0][0].shape[0]
-            mc = _budget(model)
-            Mn = mc + (128 - mc % 128)
+            Mn = _budget_rows(_budget(model))
         ctx = _native_events_ctx(model, N, (pres[0]["M"], pres[1]["M"]), Nn, Mn, bool(loss_opt.use_luma), dev)
         a = ctx["a"]
         _fill_step(ctx, a)
@@ -1016,7 +990,7 @@ def train_step_events_native(model, data, loss_opt, opt, next_data=None, side_st
                   and pres[1]["xyzs"].data_ptr() == pres[0]["xyzs"].data_ptr() + 12 * M0
                   and pres[1]["dirs"].data_ptr() == pres[0]["dirs"].data_ptr() + 12 * M0
                   and pres[1]["deltas"].data_ptr() == pres[0]["deltas"].data_ptr() + 8 * M0)
-        a.flags = 2 if merged else 0
+        a.flags = _step_flags(2 if merged else 0)
         staged = []
         if stash is not None:
             _fill_march(a, model, side_stream, perturb, dt_gamma, max_steps)
@@ -1027,7 +1001,7 @@ def train_step_events_native(model, data, loss_opt, opt, next_data=None, side_st
                 ctx["flip"][q] = which ^ 1
                 staged.append((_stage_key(no, nd, perturb, dt_gamma, max_steps), nxt))
         _fill_optimizer(ctx, a, opt)
-        carried = _call("train_step_events", a, staged)
+        carried = _call("train_step_events", a)
         # (merged, the library issued ONE grid_encode_forward / backward over 2 M points)
         for points in ([pres[0]["M"] + pres[1]["M"]] if merged else [pre["M"] for pre in pres]):
             _count_launches(points)

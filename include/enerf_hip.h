@@ -56,8 +56,10 @@ const char* enerf_last_error(void);
  * 4: enerf_stratified_*_ex (fp16 storage of the colour rows / rgb / d rgb / dx) and enerf_mlp32_io16 (16-bit I/O of the
  *    enerf_mlp32_*_p calls) added: the stratified sampler's fp16 regime.
  * 5: enerf_mesh_lattice and enerf_marching_cubes_* added (mesh export, Trainer.save_mesh).
- * 6: enerf_eval_* added (held-out metrics, Trainer.evaluate_one_epoch). */
-#define ENERF_ABI_VERSION 6
+ * 6: enerf_eval_* added (held-out metrics, Trainer.evaluate_one_epoch).
+ * 7: enerf_train_step_args gained next_count_host; `reserved` of both step structs became `report`, written by the library
+ *    (the argument pointers lost their const); flags bit 2 of both = every row through the networks. */
+#define ENERF_ABI_VERSION 7
 int enerf_abi_version(void);
 /* The library keeps grow-only scratch buffers per device (march chunk log, grid-backward record lists, ...).  Growing one
  * frees the old allocation; the counter returned here moves every time that happens.  A caller that captured library
@@ -636,9 +638,15 @@ int enerf_adam_step_multi(uint32_t count, float* const* p, float* const* g, floa
  * one by one.  What it removes is the host's work between the launches (nerf/utils.py:575-640 + main_nerf.py:211 run
  * ~60 framework calls per step).  All pointers are device pointers unless noted; every buffer is the caller's.
  * Scalar background (bg_scalar), density_scale 1, fp32 table with L = 16, C = 2, D = 3.
- * The step's MLP launches take their valid rows from its own `counter` field (NULL: every row) and their arithmetic from its
- * own `mlp_precision` field: the step neither consumes nor clears the process-wide enerf_mlp32_valid_rows,
- * enerf_mlp32_signal_next_reduce or enerf_mlp32_defer_reduce requests, and leaves enerf_mlp32_precision as it is. */
+ * The step's grid and MLP launches take their valid rows from its own `counter` field (NULL, or flags bit 2: every row) and
+ * their arithmetic from its own `mlp_precision` field; its next march takes near / far and the count mirror from the struct:
+ * the step neither consumes nor clears the process-wide enerf_mlp32_valid_rows, enerf_mlp32_signal_next_reduce,
+ * enerf_mlp32_defer_reduce, enerf_march_fuse_near_far or enerf_march_mirror_count requests, and leaves enerf_mlp32_precision
+ * as it is. */
+#define ENERF_STEP_EVERY_ROW 4u      /* `flags` bit 2 of both step structs: the grid and MLP launches take every row of the
+                                      * budget, as with counter == NULL; the compositing keeps `counter`, which it requires */
+#define ENERF_STEP_MARCH_CARRIED 1u  /* `report` bit 0 of both: the next march(es) ran in this call's own launches on `stream`;
+                                      * side_stream saw nothing (no event to wait for) */
 typedef struct enerf_train_step_args {
     uint32_t struct_bytes;              /* sizeof(enerf_train_step_args): checked */
     int mlp_precision;                  /* enerf_mlp32_precision's mode for this call's MLP launches; < 0: the process's */
@@ -666,13 +674,15 @@ typedef struct enerf_train_step_args {
     float *feats, *h32, *fb_s, *fb_c, *sigma, *rgb, *weights_sum, *image, *out_image, *g_sigmas, *g_rgbs, *dx32, *dfeat;
     /* next batch's march (next_rays_o == NULL: none).  march_flags: enerf_march_rays_train_ex's zero_unwritten bits 0-3,
      * plus bit 4 = keep this march on side_stream (the caller reads its counter back behind it there); without bit 4 the
-     * march may ride in this call's own launches on `stream` (enerf_debug_carry_count) and side_stream sees nothing */
+     * march may ride in this call's own launches on `stream` (`report` says whether it did) and side_stream sees nothing.
+     * next_count_host [host]: two words of pinned, device-visible memory, or NULL; the next march also stores its counter
+     * there (enerf_march_mirror_count's semantics, for this march only) and then never rides on `stream` */
     const float *next_rays_o, *next_rays_d, *aabb;
     const uint8_t* bitfield;
     float min_near, dt_gamma;
     uint32_t next_N, next_M, cascade, grid_size, max_steps, perturb, march_flags;
     float *next_nears, *next_fars, *next_xyzs, *next_dirs, *next_deltas;
-    int32_t *next_rays, *next_counter;
+    int32_t *next_rays, *next_counter, *next_count_host;
     /* optimizer: the table (dense gradient buffer for the levels too small to bin, zero-filled, comes back clean) and up
      * to 8 small tensors whose gradients the backward has just written through dwseg_* */
     float *table, *table_grad, *table_m, *table_v;
@@ -691,10 +701,11 @@ typedef struct enerf_train_step_args {
      * bit 1 (with bit 0, enerf_grid_owner_range set): the sharded tail that keeps this rank's slice as record lists -- the
      * backward defers, flushing only the other slices into table_grad; the caller reduce-scatters, runs
      * enerf_grid_adam_from_records_ex and all-gathers.
-     * (ABI 2: bit 2 and the three fields behind it -- the tail on the library's own RCCL communicator -- are gone.) */
-    uint32_t flags, reserved;
+     * bit 2: ENERF_STEP_EVERY_ROW.  (ABI 2 .. 6: unused, after the tail on the library's own RCCL communicator went.)
+     * report: written by the library -- zeroed at entry, ENERF_STEP_* report bits set before a call returns 0. */
+    uint32_t flags, report;
 } enerf_train_step_args;
-int enerf_train_step_mse(const enerf_train_step_args* args);
+int enerf_train_step_mse(enerf_train_step_args* args);
 /* Development aid: host microseconds enerf_train_step_mse spends in each of its calls (in call order, 16 slots, averaged
  * over the steps since timing was switched on); on >= 0 switches the timers (and clears them), on < 0 only reads. */
 int enerf_debug_step_timing(int on, double* out16);
@@ -710,8 +721,9 @@ int enerf_debug_fold_reduce(int on);
  * (extra workgroups; enerf_debug_march_carry_blocks sets how many, 0 = two per compute unit), its scan + write are one launch
  * behind it on the step's own stream -- no cross-stream signal behind the MLP backward, no event wait at the head of the next
  * step.  Same samples, same offsets.  Served where the wave-per-ray fixed-step marcher is (dt_gamma = 0, at most 16384 rays)
- * and no count mirror is armed; everything else keeps the side-stream march.  on = 0 switches it off (-1 only reads).
- * Returns the previous setting; on = -2 returns the number of steps marched that way so far. */
+ * and the call asks for no count mirror (next_count_host); everything else keeps the side-stream march.  on = 0 switches
+ * it off (-1 only reads).  Returns the previous setting; on = -2 returns the number of steps marched that way so far (a
+ * test's counter: a caller learns where its march ran from the call's own `report`). */
 int enerf_debug_carry_count(int on);
 int enerf_debug_march_carry_blocks(uint32_t blocks);
 
@@ -723,9 +735,8 @@ int enerf_debug_march_carry_blocks(uint32_t blocks);
  * mlp32_forward_p x 2, composite_rays_train_forward_blend; event_loss_fwd_bwd; per render
  * composite_rays_train_backward_mse(target = NULL), mlp32_backward_p x 2 (the second render's weight gradients are
  * added to the first's), grid_encode_backward_ex(defer, reserve = M1 + M2); grid_adam_from_records_ex.
- * As in enerf_train_step_mse, the MLP launches take their valid rows from the renders' own `counter` fields and their
- * arithmetic from `mlp_precision`: the process-wide enerf_mlp32_valid_rows, enerf_mlp32_signal_next_reduce and
- * enerf_mlp32_defer_reduce requests are neither consumed nor cleared. */
+ * As in enerf_train_step_mse, the grid and MLP launches take their valid rows from the renders' own `counter` fields and
+ * their arithmetic from `mlp_precision`: no process-wide request is consumed or cleared. */
 typedef struct enerf_step_render {
     uint32_t N, M;                      /* rays, sample rows budgeted (counter[0] real) */
     const float *xyzs, *dirs, *deltas;
@@ -779,11 +790,12 @@ typedef struct enerf_event_step_args {
      * [counter0, M) are padding whose gradients the first render's composite backward zero-fills; the MLP kernels take
      * M + min(counter1, M) as their valid-row count: enerf_mlp32_valid_rows_ex's rule); compositing and its backward stay per
      * render, on the halves.  Same per-sample values; the weight gradients are summed over both renders in one pass
-     * instead of two passes added. */
-    uint32_t flags, reserved;
+     * instead of two passes added.
+     * flags bit 2: ENERF_STEP_EVERY_ROW.  report: as in enerf_train_step_args. */
+    uint32_t flags, report;
     float *m_feats, *m_h32, *m_fb_s, *m_fb_c, *m_sigma, *m_rgb, *m_g_sigmas, *m_g_rgbs, *m_dx32, *m_dfeat;
 } enerf_event_step_args;
-int enerf_train_step_events(const enerf_event_step_args* args);
+int enerf_train_step_events(enerf_event_step_args* args);
 
 /* profiling aid: restrict grid_encode_forward/backward to the levels whose bit is set (default all) */
 int enerf_debug_grid_level_mask(uint32_t mask);

@@ -1,5 +1,6 @@
 """End-to-end behaviour of the HIP path under optimisation: the loss goes down, replicas of a step are deterministic in
 their integer state, and the rendered image agrees with the CPU oracle route in PSNR terms."""
+import contextlib
 import math
 
 import numpy as np
@@ -1086,12 +1087,31 @@ def test_weight_gradients_summed_by_the_optimizer_launch_equal_the_reduce_launch
         assert float((pa[n] - pb[n]).abs().mean()) <= 1e-4 * float(pb[n].abs().mean()) + 1e-9, n
 
 
+@contextlib.contextmanager
+def _carried_reports():
+    """Wraps fused_render._call -> the list of what every one-call step answered: bit 0 of its struct's `report`."""
+    from enerf_amd import fused_render
+    orig, seen = fused_render._call, []
+
+    def wrapped(*a):
+        seen.append(orig(*a))
+        return seen[-1]
+
+    fused_render._call = wrapped
+    try:
+        yield seen
+    finally:
+        fused_render._call = orig
+
+
 @pytest.mark.parametrize("n_rays,bound,steps", [(4096, 2, 40), (1000, 3, 36), (16384, 2, 36), (64, 2, 36)])
 def test_march_carried_by_the_optimizer_launch_equals_the_side_stream_march(n_rays, bound, steps):
     """csrc/train_step.hip: in the steady state the next batch's march rides in the table optimizer's launch (count pass) and
     one launch behind it (scan + write) instead of a second stream.  Same rays table, same counter, same samples -- bit for
     bit -- hence the same training run: 40 steps with the carried march against 40 with the side-stream march, sample
-    counters bit-exact, losses and parameters to the last bits the table's float atomics leave open."""
+    counters bit-exact, losses and parameters to the last bits the table's float atomics leave open.
+    Every call says in its struct's `report` (bit 0) whether its next march rode that way: summed over the calls, the debug
+    counter's difference."""
     from enerf_amd import _lib
     from enerf_amd.network import NeRFNetwork
     from enerf_amd.trainer import TrainHarness
@@ -1107,19 +1127,21 @@ def test_march_carried_by_the_optimizer_launch_equals_the_side_stream_march(n_ra
             model = NeRFNetwork(encoding="hashgrid", bound=bound, cuda_ray=True, out_dim_color=3).to(DEV)
             h = TrainHarness(model, lr=1e-2, occupancy="synthetic")
             losses, counters = [], []
-            for i in range(steps):
-                nxt = data[(i + 1) % 4]
-                losses.append(h.step_rgb(*data[i % 4], next_rays=(nxt[0], nxt[1])).detach().clone())
-                counters.append(model.step_counter[model.rendered_counter_slot].clone())
+            with _carried_reports() as reports:
+                for i in range(steps):
+                    nxt = data[(i + 1) % 4]
+                    losses.append(h.step_rgb(*data[i % 4], next_rays=(nxt[0], nxt[1])).detach().clone())
+                    counters.append(model.step_counter[model.rendered_counter_slot].clone())
             torch.cuda.synchronize()
             runs[carried] = (torch.stack(losses).cpu(), torch.stack(counters).cpu(),
                              {n: p.detach().clone() for n, p in model.named_parameters()},
-                             lib.enerf_debug_carry_count(-2) - taken0)
+                             lib.enerf_debug_carry_count(-2) - taken0, sum(reports))
     finally:
         lib.enerf_debug_carry_count(prev)
-    (la, ca, pa, na), (lb, cb, pb, nb) = runs[1], runs[0]
+    (la, ca, pa, na, ra), (lb, cb, pb, nb, rb) = runs[1], runs[0]
     # (the steady-state steps that have a successor to march: the cold window mirrors its count and keeps the side stream)
     assert na >= steps // 2 - 2 and nb == 0, (na, nb)
+    assert ra == na and rb == 0, (ra, na, rb)
     assert torch.equal(ca, cb)
     # (the table's smallest levels are scattered with float atomics, whose order moves last bits from run to run: the bars
     #  are those of the native-call test above)
@@ -1157,15 +1179,17 @@ def test_event_marches_carried_by_the_optimizer_launch_equal_the_side_stream_mar
             model = NeRFNetwork(encoding="hashgrid", bound=2, cuda_ray=True, out_dim_color=3).to(DEV)
             h = TrainHarness(model, lr=1e-2, occupancy="synthetic")
             torch.manual_seed(3)                               # the step draws a random background colour
-            losses = [h.step_events(batch(i), opt, next_data=batch(i + 1)).clone() for i in range(40)]
+            with _carried_reports() as reports:
+                losses = [h.step_events(batch(i), opt, next_data=batch(i + 1)).clone() for i in range(40)]
             torch.cuda.synchronize()
             runs[carried] = (torch.stack(losses).cpu(), model.step_counter.clone().cpu(),
                              {n: p.detach().clone() for n, p in model.named_parameters()},
-                             lib.enerf_debug_carry_count(-2) - taken0)
+                             lib.enerf_debug_carry_count(-2) - taken0, sum(reports))
     finally:
         lib.enerf_debug_carry_count(prev)
-    (la, ca, pa, na), (lb, cb, pb, nb) = runs[1], runs[0]
+    (la, ca, pa, na, ra), (lb, cb, pb, nb, rb) = runs[1], runs[0]
     assert na >= 20 and nb == 0, (na, nb)
+    assert ra == na and rb == 0, (ra, na, rb)      # (`report` bit 0 of every call, summed: the debug counter's difference)
     assert torch.equal(ca, cb)
     assert float(((la - lb).abs() / lb.abs().clamp(min=1e-9)).max()) <= 1e-5
     for n, a in pa.items():
@@ -1266,8 +1290,8 @@ def test_process_wide_row_count_does_not_reach_the_one_call_step():
     enerf_mlp32_valid_rows: a count of 32 rows set process-wide in front of every one-call step changes neither the samples
     nor the losses.  (Skipped rows are left unwritten in the step's own scratch: a step that honoured the setting would
     train on stale values.)
-    With `counter` NULL -- what fused_render._fill_samples passes with SKIP_PADDING_ROWS off -- every row of the budget
-    counts.  Both one-call steps' compositing needs the counter and refuses such a call (so no step can be trained that
+    With `counter` NULL every row of the budget counts (a caller that wants that AND a step sets flags bit 2 instead:
+    test_skip_padding_rows_switch_is_honoured_by_the_one_call_step).  Both one-call steps' compositing needs the counter and refuses such a call (so no step can be trained that
     way, on any commit); what the forward has written by then shows the rows its launches took: sigma and rgb of ALL rows,
     bit for bit what the same call writes with no process-wide count set.  (Before the MLP calls took their rows as an
     argument, a NULL counter left the launches to the process's setting: 32 rows written, the rest stale.)"""
@@ -1348,8 +1372,8 @@ def test_one_call_step_runs_in_its_own_arithmetic_mode():
 
 def test_one_call_step_refused_in_the_middle_leaves_nothing_armed():
     """enerf_train_step_mse takes what modifies its MLP launches (valid-row counts, the arithmetic mode, the side stream's
-    signal, the two nets' shared reduce launch) as arguments of the library's internal entry points, and disarms the march
-    one-shots its caller may have armed on the way out.  A step that is refused half-way -- here the next batch's march with
+    signal, the two nets' shared reduce launch) and its next march (near / far, the count mirror) as arguments of the
+    library's internal entry points.  A step that is refused half-way -- here the next batch's march with
     max_steps = 0, which enerf_march_rays_train_ex rejects by argument validation, after the forward and the MLP backward
     have been issued on the step's rows -- must leave nothing behind: the Python-driven steps that follow on the same model
     see the same samples and losses as on a model that never made the failing call."""
@@ -1387,4 +1411,79 @@ def test_one_call_step_refused_in_the_middle_leaves_nothing_armed():
     assert torch.equal(ca, cb)
     # (two runs of the same steps agree to the order of the float atomics of the table's smallest levels: the bound the
     #  tests above put on the same pair of routes)
+    assert np.abs(la - lb).max() <= 1e-5 * np.abs(lb).max(), (la, lb)
+
+
+def test_one_call_step_leaves_a_public_mirror_request_alone():
+    """enerf_train_step_args.next_count_host is the count mirror of the step's own next march; a request armed with
+    enerf_march_mirror_count is for the next PUBLIC march and the step neither takes nor clears it.  The cold window's last
+    call once more (its buffers and batch are alive, its next march keeps the side stream: march_flags bit 4) with A armed
+    and next_count_host = B: B receives the device counter's two words, A stays untouched, and the public count pass that
+    follows writes A -- the request survived the step -- and disarms it."""
+    import ctypes
+    from enerf_amd import _lib as L
+    from enerf_amd.backends import _raymarching as rb
+    from enerf_amd.network import NeRFNetwork
+    from enerf_amd.trainer import TrainHarness
+    lib = L.lib()
+    data = _batches(4, 1024, 2)
+    torch.manual_seed(0)
+    model = NeRFNetwork(encoding="hashgrid", bound=2, cuda_ray=True, out_dim_color=3).to(DEV)
+    h = TrainHarness(model, lr=1e-2, occupancy="synthetic")
+    _seven_steps(model, h, data)
+    a = model._native_ctx["a"]
+    assert a.next_rays_o and a.march_flags & 16
+    (stage,) = model._premarched.values()                      # the stage the call marched into, and marches into again
+    assert stage["counter"].data_ptr() == a.next_counter
+    ro, rd = (x.contiguous().view(-1, 3) for x in data[7 % 4][:2])
+    assert ro.data_ptr() == a.next_rays_o
+    A = torch.full((2,), -1, dtype=torch.int32).pin_memory()
+    B = torch.full((2,), -1, dtype=torch.int32).pin_memory()
+    rays = torch.empty(1024, 3, dtype=torch.int32, device=DEV)
+    counter = torch.zeros(2, dtype=torch.int32, device=DEV)
+
+    def public_count():
+        rb.march_rays_train_count(ro, rd, model.density_bitfield, model.bound, 0.0, 1024, 1024, model.cascade,
+                                  model.grid_size, stage["nears"], stage["fars"], rays, counter, True, 8)
+        torch.cuda.synchronize()
+
+    a.loss = None
+    try:
+        assert lib.enerf_march_mirror_count(A.data_ptr()) == 0
+        a.next_count_host = B.data_ptr()
+        assert lib.enerf_train_step_mse(ctypes.byref(a)) == 0, lib.enerf_last_error()
+        torch.cuda.synchronize()
+        assert a.report & 1 == 0
+        assert B.tolist() == stage["counter"].cpu().tolist() and B[0] > 0 and B[1] == 1024
+        assert A.tolist() == [-1, -1]
+        public_count()
+        assert A.tolist() == counter.cpu().tolist() == B.tolist()
+        A.fill_(-1)
+        public_count()                                         # ... exactly once: nothing is armed any more
+        assert A.tolist() == [-1, -1]
+    finally:
+        lib.enerf_march_mirror_count(None)
+
+
+def test_skip_padding_rows_switch_is_honoured_by_the_one_call_step(monkeypatch):
+    """fused_render.SKIP_PADDING_ROWS off (ENERF_SKIP_PADDING_ROWS=0) on the one-call step: flags bit 2 makes the grid and
+    MLP launches take every row of the budget while the compositing keeps the counter it requires.  Rows past the counter
+    get zero gradient from the compositing backward, so the steps are those of the default -- counters bit-equal, losses to
+    the order of the table's float atomics (the bar the neighbouring tests put on two runs of the same steps)."""
+    from enerf_amd import fused_render
+    from enerf_amd.network import NeRFNetwork
+    from enerf_amd.trainer import TrainHarness
+    data = _batches(4, 1024, 2)
+    runs, flags = [], []
+    for skip in (False, True):
+        monkeypatch.setattr(fused_render, "SKIP_PADDING_ROWS", skip)
+        torch.manual_seed(0)
+        model = NeRFNetwork(encoding="hashgrid", bound=2, cuda_ray=True, out_dim_color=3).to(DEV)
+        h = TrainHarness(model, lr=1e-2, occupancy="synthetic")
+        runs.append(_seven_steps(model, h, data))              # (asserts the six native calls)
+        flags.append(model._native_ctx["a"].flags)
+    (la, ca), (lb, cb) = runs
+    assert flags[0] & 4 and not flags[1] & 4, flags
+    assert torch.equal(ca, cb)
+    print("losses with every row / with the padding skipped:", la, lb)
     assert np.abs(la - lb).max() <= 1e-5 * np.abs(lb).max(), (la, lb)
