@@ -151,6 +151,10 @@ SIGNATURES = {
     "enerf_eval_stats": [_vp, _vp, _u32, _u32, _u32, _int, _int, _vp, _vp, _vp],
     "enerf_eval_correct": [_vp, _vp, _u32, _u32, _u32, _int, _vp, _vp, _vp, _vp, _vp, _vp],
     "enerf_eval_ssim": [_vp, _vp, _u32, _u32, _u32, _u32, _c.c_double, _vp, _vp, _vp],
+    "enerf_frame_batch": [_vp, _u32, _u32, _f32, _f32, _f32, _f32, _u32, _u32, _vp, _u32, _vp, _u32, _vp, _vp, _vp, _vp],
+    "enerf_error_map_sample": [_vp, _vp, _vp, _vp, _u32, _u32, _u32, _vp, _vp, _vp],
+    "enerf_error_map_update": [_vp, _vp, _vp, _u32, _vp],
+    "enerf_debug_error_map_sample_host": [_vp, _vp, _vp, _vp, _u32, _u32, _u32, _vp, _vp],
 }
 
 F32, F16, BF16 = 0, 1, 2

@@ -983,14 +983,87 @@ class TrainHarness:
         self.opt.step()
         return loss.detach()
 
+    def step_frames(self, batch, opt=None, sampler=None):
+        """One frame training step: the reference's Trainer.train_step (nerf/utils.py:575-636) + the optimizer part of
+        train_one_epoch, on a FrameSampler batch ("rays_o", "rays_d" [B,N,3], "images" [B,N,C or C+1]).  A per-pixel
+        random background (white with a background model), alpha images mixed onto it, `opt.color_space == "linear"`
+        converted, per-ray squared error; with `sampler` and the batch's "index" / "inds_coarse" the per-ray error is
+        written back into the sampler's error map.  `opt` (EventOptions-like, optional) gives out_dim_color, color_space
+        and render_kwargs.  Autograd through model.render in every regime, with that regime's optimizer and scaler
+        protocol; under strat_f16 the stratified route's fp16 regime when it serves the render."""
+        m = self.model
+        C = int(getattr(opt, "out_dim_color", None) or getattr(m, "out_dim_color", 3))
+        kw = dict(getattr(opt, "render_kwargs", None) or {})
+        kw.setdefault("out_dim_color", C)
+        rays_o, rays_d, images = batch["rays_o"], batch["rays_d"], batch["images"]
+        if getattr(opt, "color_space", "srgb") == "linear":
+            from .evaluate import srgb_to_linear
+            images = torch.cat([srgb_to_linear(images[..., :C]), images[..., C:]], dim=-1)
+        bg = 1 if m.bg_radius > 0 else torch.rand_like(images[..., :C])     # (pixel-wise random, nerf/utils.py:593)
+        if images.shape[-1] == C + 1:
+            gt = images[..., :C] * images[..., C:] + bg * (1 - images[..., C:])
+        else:
+            gt = images
+        if self.strat_f16:
+            per_ray = self._strat_f16_step(lambda: self._step_frames(rays_o, rays_d, gt, bg, kw),
+                                           self._strat_f16_ok(rays_o, rays_d, kw, bg))
+        elif self.amp_bf16 or self.amp_f16:
+            prev = self._amp_scope()
+            self.fp16 = self.amp_f16                # (fp16: the autocast route with the same scaler, as step_rgb's)
+            try:
+                per_ray = self._step_frames(rays_o, rays_d, gt, bg, kw)
+            finally:
+                self.fp16 = False
+                self._amp_restore(prev)
+        else:
+            per_ray = self._step_frames(rays_o, rays_d, gt, bg, kw)
+        if sampler is not None and "inds_coarse" in batch and "index" in batch:
+            sampler.update_error(batch["index"], batch["inds_coarse"], per_ray)
+        if self.lr_scheduler is not None:
+            self.lr_scheduler.step()
+        return per_ray.mean()
+
+    def _step_frames(self, rays_o, rays_d, gt, bg, kw):
+        """-> the per-ray loss [B,N] fp32, detached; the step is taken."""
+        if not self.model.training:
+            self.model.train()
+        self.maybe_update_extra_state()
+        self.global_step += 1
+        self.opt.zero_grad(set_to_none=True)
+
+        def forward():
+            out = self.model.render(rays_o, rays_d, staged=False, bg_color=bg, perturb=self.perturb, **kw)
+            per_ray = ((out["image"] - gt) ** 2).mean(-1)
+            return per_ray, per_ray.mean()
+        if self.fp16:
+            with torch.autocast("cuda", dtype=torch.float16, enabled=self._f16_autocast):
+                per_ray, loss = forward()
+            self.scaler.scale(loss).backward()
+            self.scaler.unscale_(self.opt)
+            self._reduce_grads()
+            self.scaler.step(self.opt)
+            self.scaler.update()
+        else:
+            per_ray, loss = forward()
+            loss.backward()
+            self._reduce_grads()
+            self.opt.step()
+        return per_ray.detach().float()
+
     def step_events(self, data, opt, next_data=None):
         """One event training step: two renders sharing one backward (nerf/utils.py:482-573)."""
         if self.strat_f16:
             # (events.train_step_events: both renders take a [B,1,C] background drawn on the device)
             bg = torch.empty((data["images"].shape[0], 1, opt.out_dim_color), device=data["rays_evs_o1"].device)
             kw = dict(opt.render_kwargs, out_dim_color=opt.render_kwargs.get("out_dim_color", opt.out_dim_color))
-            native = (opt.event_only and self._strat_f16_ok(data["rays_evs_o1"], data["rays_evs_d1"], kw, bg)
+            native = (self._strat_f16_ok(data["rays_evs_o1"], data["rays_evs_d1"], kw, bg)
                       and self._strat_f16_ok(data["rays_evs_o2"], data["rays_evs_d2"], kw, bg))
+            if native and not opt.event_only:
+                # the frame term's render (events.train_step_events): no background, or for alpha images (C + 1 = 4
+                # channels) a per-pixel one drawn like the frames' first out_dim_color channels
+                images = data["images"]
+                bg_frames = torch.empty_like(images[..., :opt.out_dim_color]) if images.shape[-1] == 4 else None
+                native = self._strat_f16_ok(data["rays_o"], data["rays_d"], kw, bg_frames)
             loss = self._strat_f16_step(lambda: self._step_events(data, opt, next_data), native)
         elif self.amp_bf16 or self.amp_f16:
             prev = self._amp_scope()

@@ -58,8 +58,9 @@ const char* enerf_last_error(void);
  * 5: enerf_mesh_lattice and enerf_marching_cubes_* added (mesh export, Trainer.save_mesh).
  * 6: enerf_eval_* added (held-out metrics, Trainer.evaluate_one_epoch).
  * 7: enerf_train_step_args gained next_count_host; `reserved` of both step structs became `report`, written by the library
- *    (the argument pointers lost their const); flags bit 2 of both = every row through the networks. */
-#define ENERF_ABI_VERSION 7
+ *    (the argument pointers lost their const); flags bit 2 of both = every row through the networks.
+ * 8: enerf_frame_batch and enerf_error_map_* added (frame batches, the reference's --error_map). */
+#define ENERF_ABI_VERSION 8
 int enerf_abi_version(void);
 /* The library keeps grow-only scratch buffers per device (march chunk log, grid-backward record lists, ...).  Growing one
  * frees the old allocation; the counter returned here moves every time that happens.  A caller that captured library
@@ -950,6 +951,38 @@ int enerf_eval_correct(const float* pred, const float* gt, uint32_t V, uint32_t 
                        double* res, double* ab, float* pred_cor, float* gt_j, enerf_stream_t stream);
 int enerf_eval_ssim(const float* x, const float* y, uint32_t V, uint32_t H, uint32_t W, uint32_t stride,
                     double data_range, void* ws, double* res, enerf_stream_t stream);
+
+/* ------------------------------------------------------------------ frame batches and the error map
+ * The frame side of the reference's collate (nerf/utils.py:111-174 get_rays, provider.py:645-663) and the error-map
+ * write-back of Trainer.train_step (nerf/utils.py:610-632), csrc/frame_batch.hip; semantics in enerf_amd/frame_sampler.py
+ * and DESIGN.md 4.12.  Every operation below is rounded to fp32 on its own (the library is built with -ffp-contract=off).
+ *
+ * frame_batch: one thread per ray.  poses [V,4,4] fp32 cam2world, view < V; pixel p = inds[k] (inds == NULL: p = k, and
+ *   N must be H*W); i = p % W, j = p / W; x = (i - cx) / fx, y = (j - cy) / fy; d = (x, y, 1) / sqrt(x^2 + y^2 + 1);
+ *   rays_d[k] = R d, rays_o[k] = t of poses[view]; target[k, :] = images[view, p, :] with images [V,H,W,Ci] fp32,
+ *   Ci in 1..4 (images == NULL: target is not written).  A pixel outside [0, H*W) reads nothing and gives NaN rows.
+ * error_map_sample: ONE workgroup, the ENERF_ERROR_MAP_CELLS cells sorted in LDS.  weights, e fp32 [16384];
+ *   key_c = weights[c] > 0 ? weights[c] / e[c] : 0 (IEEE fp32; e[c] == 0 gives +inf); the N <= 16384 cells of the largest
+ *   key, ties to the smaller cell index, go to inds_coarse i64 [N] in that order: sampling without replacement with
+ *   probability proportional to the weights when e holds independent Exp(1) draws.  Cells of weight <= 0 sort last and
+ *   are taken only when fewer than N cells are positive (torch.multinomial raises there).  weights == NULL: inds_coarse
+ *   is read instead of written (the selection is skipped).  Then, with r = c / 128, q = c % 128, sx = fp32(H / 128.0),
+ *   sy = fp32(W / 128.0): row = min((int64)(fp32(r) sx + u_row[k] sx), H - 1), col likewise with q, sy, u_col, W - 1;
+ *   inds[k] = row W + col, i64 [N].  u_row, u_col fp32 [N] in [0, 1).
+ * error_map_update: one thread per ray; map[inds_coarse[k]] = fp32(0.1) map[inds_coarse[k]] + fp32(0.9) err[k] on the
+ *   view's row map [16384].  inds_coarse must hold no duplicates (it comes from the selection above): no atomics.  A
+ *   cell outside [0, 16384) is skipped. */
+#define ENERF_ERROR_MAP_CELLS 16384
+int enerf_frame_batch(const float* poses, uint32_t V, uint32_t view, float fx, float fy, float cx, float cy, uint32_t H,
+                      uint32_t W, const int64_t* inds, uint32_t N, const float* images, uint32_t Ci, float* rays_o,
+                      float* rays_d, float* target, enerf_stream_t stream);
+int enerf_error_map_sample(const float* weights, const float* e, const float* u_row, const float* u_col, uint32_t N,
+                           uint32_t H, uint32_t W, int64_t* inds_coarse, int64_t* inds, enerf_stream_t stream);
+int enerf_error_map_update(float* map, const int64_t* inds_coarse, const float* err, uint32_t N, enerf_stream_t stream);
+/* error_map_sample's sorting network and pixel mapping run on the HOST, thread by thread, on host pointers (tests without
+ * a GPU hold the network to the statement with it). */
+int enerf_debug_error_map_sample_host(const float* weights, const float* e, const float* u_row, const float* u_col,
+                                      uint32_t N, uint32_t H, uint32_t W, int64_t* inds_coarse, int64_t* inds);
 
 #ifdef __cplusplus
 }
