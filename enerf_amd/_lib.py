@@ -124,6 +124,7 @@ SIGNATURES = {
     "enerf_nerf_mlp_available": [],
     "enerf_amp_armed": [],
     "enerf_debug_nerf_mlp_fused": [_int],
+    "enerf_debug_nerf_bwd_transpose": [_int],
     "enerf_debug_nerf_frags_copy": [_vp, _vp],
     "enerf_debug_carry_frags": [_int],
     "enerf_debug_carry_count": [_int],

@@ -179,7 +179,7 @@ __device__ __forceinline__ void copy_frags(u32x4n* __restrict__ fr, const uint32
 // split8 / exact8 the kernel is bit-stable at any residency (tools/nerf_fwd_residency.py: 0 of 400 launches at three
 // workgroups per CU, padded and unpadded builds; tests/test_gpu_mlp32.py soaks it), and the forward shares the CU again:
 // 48 KiB of LDS, ~136 registers, three workgroups per CU = three wavefronts per SIMD hiding each other's MFMA and LDS
-// latencies.  The backward keeps a CU to itself for what it needs (149 KiB of LDS, ~480 registers).
+// latencies.  The backward keeps a CU to itself for what it needs (149 / 160 KiB of LDS, ~480 registers).
 // (-DNERF_FWD_ONE_PER_CU: the forward as shipped in round 5's first half, for A/B runs.)
 #ifndef NERF_FWD_ONE_PER_CU
 #define NERF_FWD_WHOLE_SIMD() do {} while (0)
@@ -318,7 +318,8 @@ struct NerfBwdArgs {
 };
 
 // Register budget: the twelve weight-gradient accumulators (192 registers) live in the AGPR half of the file; the arch
-// half holds a tile's working set, which therefore must stay small: the selection matrices of the flips sit in LDS, and the
+// half holds a tile's working set, which therefore must stay small: the selection matrices of the flips (FLIP_MFMA, below)
+// sit in LDS, and the
 // two hidden activations that are needed again much later (sigma net hidden layer, colour net first layer) are stashed in
 // LDS as the operand halves they were split into (a private 16 KiB per wave: no fence, no barrier) -- the ReLU mask of the
 // backward is read off the stashed hi half (an activation is positive iff its bf16 rounding is non-zero).
@@ -326,11 +327,37 @@ constexpr uint32_t kSelWords = 5 * 256;                                  // five
 constexpr uint32_t kStashWords = 8 * 512;                                // per wave: 2 layers x [2 blocks][2 K-steps] fragments
 constexpr uint32_t kBwdLdsWords = NF_BWD * kFragWords + kSelWords + 4 * kStashWords;
 
-// g[q] = (element q of the tile whose K-step fragments are f[0], f[1] is non-zero) ? g[q] : 0   (hi halves: bf16 pairs)
-__device__ __forceinline__ void mask_by_frag(f32x16& g, const FragT<3> (&f)[2]) {
+// How an operand of a weight-gradient product (which contracts over the samples a D tile keeps on the lanes) is transposed.
+//   FLIP_MFMA: on the matrix pipe, by products with 0/1 selection matrices (flip_tile / flip_natural of mlp32s_ops.h);
+//   FLIP_LDS : through a per-wave LDS image [32 samples][32 neurons] of the 16-bit halves, 64-byte rows: the lane of sample j
+//              stores its packed quads (8 bytes: neurons 4k .. 4k+3 of K-step t = k / 4) into row j, and ds_read_b64_tr_b16
+//              hands lane (c, h) neuron c of samples 16t + 8u + 4h + 0..3 -- elements 4u .. 4u+3 of K-step t, the very
+//              slots the selection matrices fill (nrow(8t + e, h)): every weight-gradient MFMA sees the same operand bits.
+//              The 8-byte chunk k of row j sits at chunk position k ^ ((j >> 1) & 7): a transposed read takes four whole
+//              rows per 32-lane half (256 contiguous bytes, every bank once) whatever the permutation inside a row, and the
+//              sixteen lanes of a ds_write_b64 group, one row each, then cover all 32 banks instead of 4.
+//              Five images of 4 KiB (hi + lo) per wave: the two stashed activations (read by rows for the ReLU mask AND
+//              transposed for the weight gradient -- no second copy), and one scratch; an image takes the next operand as
+//              soon as its tenant is dead.  A wave's LDS operations execute in order and the images are private to the
+//              wave: no barrier, no wait between a store and the read of another lane's data.
+enum { FLIP_MFMA = 0, FLIP_LDS = 1 };
+constexpr uint32_t kImgBytes = 4096, kImgLo = 2048, kWaveImages = 5;
+constexpr uint32_t kBwdLdsWordsTr = NF_BWD * kFragWords + 4 * kWaveImages * (kImgBytes / 4);
+typedef short s16x4 __attribute__((ext_vector_type(4)));
+typedef __attribute__((address_space(3))) s16x4 lds_s16x4;
+__device__ __forceinline__ bf16x8 tr_read8(const unsigned char* p0, const unsigned char* p1) {
+    const s16x4 lo4 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)p0);       // ds_read_b64_tr_b16
+    const s16x4 hi4 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)p1);
+    return __builtin_bit_cast(bf16x8, __builtin_shufflevector(lo4, hi4, 0, 1, 2, 3, 4, 5, 6, 7));
+}
+// the compiler reasons about one lane's addresses; a transposed read takes other lanes' stores
+#define NERF_IMG_FENCE() asm volatile("" ::: "memory")
+
+// g[q] = (element q of the tile whose K-step fragments' hi halves are hi[0], hi[1] is non-zero) ? g[q] : 0   (bf16 pairs)
+__device__ __forceinline__ void mask_by_hi(f32x16& g, const bf16x8 (&hi)[2]) {
 #pragma unroll
     for (int t = 0; t < 2; t++) {
-        const i32x4 w = __builtin_bit_cast(i32x4, f[t].hi);
+        const i32x4 w = __builtin_bit_cast(i32x4, hi[t]);
 #pragma unroll
         for (int p = 0; p < 4; p++) {
             const uint32_t u = (uint32_t)w[p];
@@ -339,15 +366,23 @@ __device__ __forceinline__ void mask_by_frag(f32x16& g, const FragT<3> (&f)[2]) 
         }
     }
 }
+__device__ __forceinline__ void mask_by_frag(f32x16& g, const FragT<3> (&f)[2]) {
+    const bf16x8 hi[2] = {f[0].hi, f[1].hi};
+    mask_by_hi(g, hi);
+}
 
-__global__ void __launch_bounds__(256) k_nerf_bwd(NerfBwdArgs a, const uint32_t* __restrict__ frags, ShNorm4 nrm) {
-    __shared__ __attribute__((aligned(16))) uint32_t lds[kBwdLdsWords];       // operands (then the dW sums), selectors, stashes
+// The kernel's body; `lds`: the workgroup's kBwdLdsWords (FLIP_MFMA: operands, then the dW sums; selectors; stashes) or
+// kBwdLdsWordsTr (FLIP_LDS: operands; five images per wave) dwords.
+template <int TR>
+__device__ __forceinline__ void nerf_bwd_body(uint32_t* lds, const NerfBwdArgs& a, const uint32_t* __restrict__ frags,
+                                              const ShNorm4& nrm) {
     static_assert(NF_BWD * kFragWords >= 2 * P_STRIDE, "the two sum regions reuse the operand area");
-    static_assert(kBwdLdsWords * 4 <= 160 * 1024, "LDS");
+    static_assert(kBwdLdsWords * 4 <= 160 * 1024 && kBwdLdsWordsTr * 4 <= 160 * 1024, "LDS");
 #if defined(MLP32S_NO_OPERAND_BARRIER)
     // nerf_mlp_bwd.hip compiles this kernel without the operand barrier: sound only while ONE workgroup of it fits a CU,
     // i.e. one wavefront per SIMD (mlp32s_ops.h: operand_ready).  More than half of the CU's 160 KiB of LDS guarantees it.
-    static_assert(kBwdLdsWords * 4 > 80 * 1024, "k_nerf_bwd without the operand barrier must stay at one workgroup per CU");
+    static_assert(kBwdLdsWords * 4 > 80 * 1024 && kBwdLdsWordsTr * 4 > 80 * 1024,
+                  "k_nerf_bwd without the operand barrier must stay at one workgroup per CU");
 #endif
     NERF_WHOLE_SIMD();
     typedef FragT<3> Frag;
@@ -386,7 +421,7 @@ __global__ void __launch_bounds__(256) k_nerf_bwd(NerfBwdArgs a, const uint32_t*
     u32x4n* stash = sel + 5 * 64 + wid * (kStashWords / 4);      // this wave's: [layer][block][K-step][hi, lo][lane]
     copy_frags<20>(fr, frags, 0, 0);
     copy_frags<20>(fr, frags, B_COT, 20);
-    if (wid == 0) {
+    if (TR == FLIP_MFMA && wid == 0) {
         // selection matrices of the flips: natural order (dL/dY), a tile's two register halves, and X^T (K-step t of the
         // input operand holds input columns kmap<1>(8t + e, h))
         sel[0 * 64 + lane] = __builtin_bit_cast(u32x4n, selector(j, h, 0));
@@ -423,6 +458,92 @@ __global__ void __launch_bounds__(256) k_nerf_bwd(NerfBwdArgs a, const uint32_t*
             const u32x4n* p = stash + (((layer * 2 + ib) * 2 + t) * 2) * 64 + lane;
             f[t].hi = __builtin_bit_cast(bf16x8, p[0]);
             f[t].lo = __builtin_bit_cast(bf16x8, p[64]);
+        }
+    };
+    // ---- FLIP_LDS: this wave's images 0, 1 (sigma net hidden layer), 2, 3 (colour net first layer), 4 (scratch); byte offsets
+    // inside an image half.  Stores: row j, chunk k at wr0 ^ (8 * (k ^ h)) for the quads of a D tile's operands (k = 4t + 2u + h),
+    // wn0 ^ 8u for an operand in natural order (k = 2h + u), wx0 ^ 8k (+ 4h inside the chunk) for the pairs of X's operands.
+    // Transposed reads: lane 4q + p of a 16-lane group supplies row 16t + 8u + 4h + q, chunk 4 (j / 16) + p.
+    unsigned char* img0 = reinterpret_cast<unsigned char*>(fr + NF_BWD * 128) + wid * (kWaveImages * kImgBytes);
+    const uint32_t swz = (uint32_t)(j >> 1) & 7u;
+    const uint32_t wr0 = 64u * j + 8u * ((uint32_t)h ^ swz);
+    const uint32_t wn0 = 64u * j + 8u * ((uint32_t)(2 * h) ^ swz);
+    const uint32_t wx0 = 64u * j + 8u * swz + 4u * h;
+    auto tr_off = [&](int u) -> uint32_t {
+        const uint32_t row = 8u * u + 4u * h + (uint32_t)((j & 15) >> 2), k = 4u * (j >> 4) + (uint32_t)(j & 3);
+        return 64u * row + 8u * (k ^ ((row >> 1) & 7u));                 // (+ 1024 t: sixteen rows on, the same swizzle)
+    };
+    const uint32_t tr0 = tr_off(0), tr1 = tr_off(1);
+    auto put_quads = [&](unsigned char* p, const bf16x8& v, uint32_t at) {         // elements 0..3 -> at, 4..7 -> at ^ 16
+        const i32x4 w = __builtin_bit_cast(i32x4, v);
+        *reinterpret_cast<uint2*>(p + at) = make_uint2((uint32_t)w[0], (uint32_t)w[1]);
+        *reinterpret_cast<uint2*>(p + (at ^ 16u)) = make_uint2((uint32_t)w[2], (uint32_t)w[3]);
+    };
+    auto put_img = [&](int img, const Frag (&f)[2]) {    // the operands of a D tile (or of the colour net's input)
+        unsigned char* p = img0 + img * kImgBytes;
+        NERF_IMG_FENCE();
+#pragma unroll
+        for (int t = 0; t < 2; t++) {
+            put_quads(p, f[t].hi, wr0 ^ (32u * t));
+            put_quads(p + kImgLo, f[t].lo, wr0 ^ (32u * t));
+        }
+        NERF_IMG_FENCE();
+    };
+    auto put_nat = [&](int img, const Frag& f, bool acc_order) {      // one K-step of outputs: 8h + e, or nrow(e, h)
+        unsigned char* p = img0 + img * kImgBytes;
+        NERF_IMG_FENCE();
+        if (acc_order) {
+            put_quads(p, f.hi, wr0);
+            put_quads(p + kImgLo, f.lo, wr0);
+        } else {
+            const i32x4 wh = __builtin_bit_cast(i32x4, f.hi), wl = __builtin_bit_cast(i32x4, f.lo);
+#pragma unroll
+            for (int u = 0; u < 2; u++) {
+                *reinterpret_cast<uint2*>(p + (wn0 ^ (8u * u))) = make_uint2((uint32_t)wh[2 * u], (uint32_t)wh[2 * u + 1]);
+                *reinterpret_cast<uint2*>(p + kImgLo + (wn0 ^ (8u * u))) = make_uint2((uint32_t)wl[2 * u], (uint32_t)wl[2 * u + 1]);
+            }
+        }
+        NERF_IMG_FENCE();
+    };
+    auto put_x = [&](int img, const Frag (&f)[2]) {      // X's operands: element pair m of K-step t = columns 16t + 4m + 2h + {0, 1}
+        unsigned char* p = img0 + img * kImgBytes;
+        NERF_IMG_FENCE();
+#pragma unroll
+        for (int t = 0; t < 2; t++) {
+            const i32x4 wh = __builtin_bit_cast(i32x4, f[t].hi), wl = __builtin_bit_cast(i32x4, f[t].lo);
+#pragma unroll
+            for (int m = 0; m < 4; m++) {
+                *reinterpret_cast<uint32_t*>(p + (wx0 ^ (32u * t + 8u * m))) = (uint32_t)wh[m];
+                *reinterpret_cast<uint32_t*>(p + kImgLo + (wx0 ^ (32u * t + 8u * m))) = (uint32_t)wl[m];
+            }
+        }
+        NERF_IMG_FENCE();
+    };
+    auto get_T = [&](int img, Frag (&out)[2]) {          // the image's transpose: what flip_tile returns
+        const unsigned char* p = img0 + img * kImgBytes;
+#pragma unroll
+        for (int t = 0; t < 2; t++) {
+            out[t].hi = tr_read8(p + 1024 * t + tr0, p + 1024 * t + tr1);
+            out[t].lo = tr_read8(p + kImgLo + 1024 * t + tr0, p + kImgLo + 1024 * t + tr1);
+        }
+    };
+    auto get_T_nat = [&](int img, Frag (&out)[2]) {      // what flip_natural returns: outputs 16..31 do not exist (a select: the
+        get_T(img, out);                                 // transposed read itself needs every lane)
+#pragma unroll
+        for (int t = 0; t < 2; t++) {
+            const i32x4 zh = __builtin_bit_cast(i32x4, out[t].hi), zl = __builtin_bit_cast(i32x4, out[t].lo);
+            out[t].hi = __builtin_bit_cast(bf16x8, j < 16 ? zh : (i32x4)(0));
+            out[t].lo = __builtin_bit_cast(bf16x8, j < 16 ? zl : (i32x4)(0));
+        }
+    };
+    auto get_rows_hi = [&](int img, bf16x8 (&hi)[2]) {   // the hi halves as put_img stored them (the ReLU mask's source)
+        const unsigned char* p = img0 + img * kImgBytes;
+#pragma unroll
+        for (int t = 0; t < 2; t++) {
+            const uint2 q0 = *reinterpret_cast<const uint2*>(p + (wr0 ^ (32u * t)));
+            const uint2 q1 = *reinterpret_cast<const uint2*>(p + (wr0 ^ (32u * t) ^ 16u));
+            const i32x4 w = {(int)q0.x, (int)q0.y, (int)q1.x, (int)q1.y};
+            hi[t] = __builtin_bit_cast(bf16x8, w);
         }
     };
 
@@ -467,7 +588,8 @@ __global__ void __launch_bounds__(256) k_nerf_bwd(NerfBwdArgs a, const uint32_t*
                 for (int t = 0; t < 2; t++) t0 = mmap(get(F_S0 + 2 * ob + t), xop[t], t0);
                 relu_tile(t0);
                 split_tile<3>(t0, af[ob]);
-                put_stash(0, ob, af[ob]);
+                if constexpr (TR == FLIP_LDS) put_img(ob, af[ob]);
+                else put_stash(0, ob, af[ob]);
             }
 #pragma unroll
             for (int ib = 0; ib < 2; ib++)
@@ -494,7 +616,8 @@ __global__ void __launch_bounds__(256) k_nerf_bwd(NerfBwdArgs a, const uint32_t*
                 for (int t = 0; t < 2; t++) t0 = mmap(get(F_C0 + 2 * ob + t), inop[t], t0);
                 relu_tile(t0);
                 split_tile<3>(t0, af[ob]);
-                put_stash(1, ob, af[ob]);
+                if constexpr (TR == FLIP_LDS) put_img(2 + ob, af[ob]);
+                else put_stash(1, ob, af[ob]);
             }
 #pragma unroll
             for (int ob = 0; ob < 2; ob++) {
@@ -532,7 +655,30 @@ __global__ void __launch_bounds__(256) k_nerf_bwd(NerfBwdArgs a, const uint32_t*
         const float dsig = valid ? (ds_raw * a.sigma_scale) * expf(fminf(fmaxf(h0, -15.0f), 15.0f)) : 0.0f;
         request_out(tnext);
         Frag gf[2][2], gT[2][2];                         // a layer's output gradient: as operands, and flipped
-        {
+        if constexpr (TR == FLIP_LDS) {
+            // everything passes through the scratch image, in program order (a store follows the reads of its predecessor)
+            Frag dyT[2];
+            put_nat(4, dyf, false);
+            get_T_nat(4, dyT);
+            put_img(4, c1f[0]);
+#pragma unroll
+            for (int ib = 0; ib < 2; ib++) {
+                f32x16 g = mmap(get(B_COT + ib), dyf, (f32x16)(0.0f));
+                mask_by_frag(g, c1f[ib]);
+                Frag ft[2];
+                get_T(4, ft);
+                if (ib == 0) put_img(4, c1f[1]);
+#pragma unroll
+                for (int t = 0; t < 2; t++) awoC[ib] = mmap(dyT[t], ft[t], awoC[ib]);
+                split_tile<3>(g, gf[ib]);
+            }
+#pragma unroll
+            for (int ib = 0; ib < 2; ib++) {
+                put_img(4, gf[ib]);
+                get_T(4, gT[ib]);
+            }
+            put_img(4, inop);                            // (waits there for the colour net's input layer)
+        } else {
             Frag dyT[2];
             flip_natural<3>(dyf, SEL(0), dyT);
 #pragma unroll
@@ -549,7 +695,35 @@ __global__ void __launch_bounds__(256) k_nerf_bwd(NerfBwdArgs a, const uint32_t*
             for (int ib = 0; ib < 2; ib++) flip_tile<3>(gf[ib], SEL(1), SEL(2), gT[ib]);
         }
         // ---- colour net, hidden layer
-        {
+        if constexpr (TR == FLIP_LDS) {
+            Frag g0f[2][2];
+#pragma unroll
+            for (int ib = 0; ib < 2; ib++) {
+                f32x16 n = (f32x16)(0.0f);
+#pragma unroll
+                for (int ob = 0; ob < 2; ob++)
+#pragma unroll
+                    for (int t = 0; t < 2; t++) n = mmap(get(B_CHT + (ib * 2 + ob) * 2 + t), gf[ob][t], n);
+                bf16x8 c0hi[2];
+                Frag ft[2];
+                get_rows_hi(2 + ib, c0hi);
+                mask_by_hi(n, c0hi);
+                get_T(2 + ib, ft);
+#pragma unroll
+                for (int ob = 0; ob < 2; ob++)
+#pragma unroll
+                    for (int t = 0; t < 2; t++) awhC[ob][ib] = mmap(gT[ob][t], ft[t], awhC[ob][ib]);
+                split_tile<3>(n, g0f[ib]);
+                put_img(2 + ib, g0f[ib]);                // (the stashed activation is dead: its image takes the gradient)
+            }
+#pragma unroll
+            for (int ib = 0; ib < 2; ib++) {
+                gf[ib][0] = g0f[ib][0];
+                gf[ib][1] = g0f[ib][1];
+                get_T(2 + ib, gT[ib]);
+            }
+            put_x(2, xop);                               // (waits there for the sigma net's input layer)
+        } else {
             Frag g0f[2][2];
 #pragma unroll
             for (int ib = 0; ib < 2; ib++) {
@@ -580,7 +754,8 @@ __global__ void __launch_bounds__(256) k_nerf_bwd(NerfBwdArgs a, const uint32_t*
         Frag dysf;
         {
             Frag inT[2];
-            flip_tile<3>(inop, SEL(1), SEL(2), inT);
+            if constexpr (TR == FLIP_LDS) get_T(4, inT);
+            else flip_tile<3>(inop, SEL(1), SEL(2), inT);
 #pragma unroll
             for (int ob = 0; ob < 2; ob++)
 #pragma unroll
@@ -598,7 +773,26 @@ __global__ void __launch_bounds__(256) k_nerf_bwd(NerfBwdArgs a, const uint32_t*
             dysf = split8<3>(dys);
         }
         // ---- sigma net, output layer
-        {
+        if constexpr (TR == FLIP_LDS) {
+            Frag dyT[2];
+            put_nat(4, dysf, true);                      // (slots in accumulator order)
+            get_T_nat(4, dyT);
+#pragma unroll
+            for (int ib = 0; ib < 2; ib++) {
+                f32x16 g = mmap(get(B_SOT + ib), dysf, (f32x16)(0.0f));
+                bf16x8 ashi[2];
+                Frag ft[2];
+                get_rows_hi(ib, ashi);
+                mask_by_hi(g, ashi);
+                get_T(ib, ft);
+#pragma unroll
+                for (int t = 0; t < 2; t++) awoS[ib] = mmap(dyT[t], ft[t], awoS[ib]);
+                split_tile<3>(g, gf[ib]);
+                put_img(ib, gf[ib]);
+            }
+#pragma unroll
+            for (int ib = 0; ib < 2; ib++) get_T(ib, gT[ib]);
+        } else {
             Frag dyT[2];
             flip_natural<3>(dysf, SEL(1), dyT);          // (slots in accumulator order: the first half's selection matrix)
 #pragma unroll
@@ -618,7 +812,8 @@ __global__ void __launch_bounds__(256) k_nerf_bwd(NerfBwdArgs a, const uint32_t*
         // ---- sigma net, input layer
         {
             Frag xT[2];
-            flip_tile<3>(xop, SEL(3), SEL(4), xT);
+            if constexpr (TR == FLIP_LDS) get_T(2, xT);
+            else flip_tile<3>(xop, SEL(3), SEL(4), xT);
 #pragma unroll
             for (int ob = 0; ob < 2; ob++)
 #pragma unroll
@@ -675,6 +870,17 @@ __global__ void __launch_bounds__(256) k_nerf_bwd(NerfBwdArgs a, const uint32_t*
     for (uint32_t i = threadIdx.x; i < NW_S + NW_C; i += blockDim.x) dst[i] = r0[i] + r0[P_STRIDE + i];
 }
 
+// The two forms as kernels: k_nerf_bwd transposes through LDS (the default), k_nerf_bwd_mfma on the matrix pipe (the form
+// shipped before; enerf_debug_nerf_bwd_transpose(0) selects it for A/B runs and for the bit-identity test).
+__global__ void __launch_bounds__(256) k_nerf_bwd(NerfBwdArgs a, const uint32_t* __restrict__ frags, ShNorm4 nrm) {
+    __shared__ __attribute__((aligned(16))) uint32_t lds[kBwdLdsWordsTr];
+    nerf_bwd_body<FLIP_LDS>(lds, a, frags, nrm);
+}
+__global__ void __launch_bounds__(256) k_nerf_bwd_mfma(NerfBwdArgs a, const uint32_t* __restrict__ frags, ShNorm4 nrm) {
+    __shared__ __attribute__((aligned(16))) uint32_t lds[kBwdLdsWords];
+    nerf_bwd_body<FLIP_MFMA>(lds, a, frags, nrm);
+}
+
 #endif
 // ---------------------------------------------------------------------------------------------------- launchers
 #ifdef NERF_MLP_BACKWARD_UNIT
@@ -701,6 +907,10 @@ void nerf_launch_fwd(const float* X, const float* dirs, const uint32_t* frags, f
 }
 
 #else
+#ifndef NERF_BWD_TRANSPOSE_DEFAULT
+#define NERF_BWD_TRANSPOSE_DEFAULT 1
+#endif
+static int g_nerf_bwd_transpose = NERF_BWD_TRANSPOSE_DEFAULT;      // enerf_debug_nerf_bwd_transpose
 void nerf_launch_bwd(const float* X, const float* dirs, const float* g_rgb, const float* rgb, const float* g_sigma,
                      float sigma_scale, const uint32_t* frags, float* dX, float* partial, uint32_t B, uint32_t out_c,
                      const int32_t* valid_rows, uint32_t valid_base, uint32_t valid_cap, uint32_t grid, hipStream_t s,
@@ -710,8 +920,21 @@ void nerf_launch_bwd(const float* X, const float* dirs, const float* g_rgb, cons
     a.X = X; a.dirs = dirs; a.g_rgb = g_rgb; a.rgb = rgb; a.g_sigma = g_sigma; a.sigma_scale = sigma_scale;
     a.dX = dX; a.partial = partial; a.B = B; a.out_c = out_c;
     a.rows = NerfRows{valid_rows, valid_base, valid_cap};
-    hipExtLaunchKernelGGL(k_nerf_bwd, dim3(grid), dim3(256), 0, s, nullptr, ev_stop, 0, a, frags, make_sh_norm4());
+    if (g_nerf_bwd_transpose)
+        hipExtLaunchKernelGGL(k_nerf_bwd, dim3(grid), dim3(256), 0, s, nullptr, ev_stop, 0, a, frags, make_sh_norm4());
+    else
+        hipExtLaunchKernelGGL(k_nerf_bwd_mfma, dim3(grid), dim3(256), 0, s, nullptr, ev_stop, 0, a, frags, make_sh_norm4());
 }
 #endif
 
 }  // namespace enerf_mlp32
+
+#ifdef NERF_MLP_BACKWARD_UNIT
+// testing aid (include/enerf_hip.h): how k_nerf_bwd transposes its weight-gradient operands -- 0: on the matrix pipe,
+// 1: through LDS (default); -1 queries; returns the previous value
+extern "C" int enerf_debug_nerf_bwd_transpose(int mode) {
+    const int prev = enerf_mlp32::g_nerf_bwd_transpose;
+    if (mode >= 0) enerf_mlp32::g_nerf_bwd_transpose = mode != 0 ? 1 : 0;
+    return prev;
+}
+#endif

@@ -59,8 +59,9 @@ const char* enerf_last_error(void);
  * 6: enerf_eval_* added (held-out metrics, Trainer.evaluate_one_epoch).
  * 7: enerf_train_step_args gained next_count_host; `reserved` of both step structs became `report`, written by the library
  *    (the argument pointers lost their const); flags bit 2 of both = every row through the networks.
- * 8: enerf_frame_batch and enerf_error_map_* added (frame batches, the reference's --error_map). */
-#define ENERF_ABI_VERSION 8
+ * 8: enerf_frame_batch and enerf_error_map_* added (frame batches, the reference's --error_map).
+ * 9: enerf_debug_nerf_bwd_transpose added (how the fused MLP backward transposes its weight-gradient operands). */
+#define ENERF_ABI_VERSION 9
 int enerf_abi_version(void);
 /* The library keeps grow-only scratch buffers per device (march chunk log, grid-backward record lists, ...).  Growing one
  * frees the old allocation; the counter returned here moves every time that happens.  A caller that captured library
@@ -466,6 +467,10 @@ int enerf_mlp32_backward_p(const float* dY, const float* X, const float* const* 
  * follows; dwseg_* are not written by this call. */
 int enerf_nerf_mlp_available(void);
 int enerf_debug_nerf_mlp_fused(int on);
+/* Testing aid, process-wide: how enerf_nerf_mlp_backward's kernel transposes the operands of its weight-gradient products.
+ * 0: on the matrix pipe (products with 0/1 selection matrices), 1: through LDS with transposed reads (default; the same
+ * operand bits, so the same gradients), -1: query only.  Returns the previous value. */
+int enerf_debug_nerf_bwd_transpose(int mode);
 /* Testing aid: the operand fragments (44 x 2048 bytes) as the last build left them, copied to device memory `dst`. */
 int enerf_debug_nerf_frags_copy(void* dst, enerf_stream_t stream);
 int enerf_nerf_mlp_forward(const float* feats, const float* dirs, const float* const* wseg_s, const float* const* wseg_c,
