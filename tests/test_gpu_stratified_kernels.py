@@ -40,6 +40,8 @@ import numpy as np
 import pytest
 import torch
 
+from nerf_mlp_ref import sh64 as _sh64
+
 pytestmark = pytest.mark.gpu
 DEV = "cuda"
 U = 2.0 ** -24
@@ -283,20 +285,6 @@ def _bg(c, seed):
 def _storage(storage):
     L = _lib()
     return (L.F16, torch.float16) if storage == "f16" else (L.F32, torch.float32)
-
-
-def _sh64(d):
-    """The 16 real spherical harmonics of degree < 4 (shencoder.cu's polynomials) in float64."""
-    x, y, z = d[:, 0], d[:, 1], d[:, 2]
-    xy, yz, xz, x2, y2, z2 = x * y, y * z, x * z, x * x, y * y, z * z
-    return torch.stack([
-        torch.full_like(x, 0.28209479177387814), -0.48860251190291987 * y, 0.48860251190291987 * z,
-        -0.48860251190291987 * x, 1.0925484305920792 * xy, -1.0925484305920792 * yz,
-        0.94617469575755997 * z2 - 0.31539156525251999, -1.0925484305920792 * xz,
-        0.54627421529603959 * x2 - 0.54627421529603959 * y2, 0.59004358992664352 * y * (-3.0 * x2 + y2),
-        2.8906114426405538 * xy * z, 0.45704579946446572 * y * (1.0 - 5.0 * z2),
-        0.3731763325901154 * z * (5.0 * z2 - 3.0), 0.45704579946446572 * x * (1.0 - 5.0 * z2),
-        1.4453057213202769 * z * (x2 - y2), 0.59004358992664352 * x * (-x2 + 3.0 * y2)], -1)
 
 
 def _check_pad(buf, total, cap, what):
