@@ -16,7 +16,7 @@ budget would keep).  A 4096-ray step is otherwise bounded by the host's launch r
 """
 import torch
 
-from . import scene
+from . import dp_tail, scene
 from .optim import FusedAdam
 from .parallel import GradAverager
 
@@ -440,12 +440,10 @@ class TrainHarness:
         # buffer is kept when the previous step's Adam pass cleared it (step_now(zero_grads=True)): the grid backward
         # then adds straight into it, with no 52 MB allocation and fill
         emb = m._modules["encoder"]._parameters["embeddings"]
-        keep = emb.grad if (not self.use_graphs and self._cleared_grad is not None
-                            and emb.grad is self._cleared_grad) else None
-        self._cleared_grad = None
+        keep = self._reuse_cleared_grad(emb)
         for p in self._params:
             p.grad = None
-        if keep is not None:
+        if keep is not None and not self.use_graphs:
             emb.grad = keep
         loss = None
         if not self.use_graphs:                     # (a captured graph would always accumulate into the same slot)
@@ -458,7 +456,7 @@ class TrainHarness:
                                                    after_forward=after_forward, loss_out=loss, raw=raw,
                                                    defer_table=defer_table, after_mlp_backward=after_mlp_backward)
         if raw:
-            self._raw_grads = grads                 # (embedding gradient, flat dW): _finish_distributed takes over
+            self._raw_grads = grads                 # (embedding gradient, flat dW): dp_tail.finish takes over
         else:
             for p, g in zip(fused_network.network_params(m), grads):
                 if g is not None:
@@ -468,130 +466,13 @@ class TrainHarness:
         with torch.no_grad():
             return torch.nn.functional.mse_loss(image, target.view(-1, 3))
 
-    def _finish_distributed(self, issue_prefetch=None):
-        """Data-parallel tail of the closed-form step: the hash-table gradient is all-reduced in `comm_chunks` pieces
-        and Adam runs on each piece as it lands (the optimizer pass over the table hides under the remaining
-        collectives); the MLP gradients travel as the backward's one flat dW buffer."""
-        import torch.distributed as dist
-        from . import fused_network
-        m = self.model
-        g_emb, dw = self._raw_grads
-        self._raw_grads = None
-        emb = m.encoder.embeddings
-        if g_emb is None:
-            g_emb = emb.grad                                  # the kept buffer: the grid backward added into it
-        else:
-            emb.grad = g_emb
-        nccl = dist.get_backend() == "nccl"                 # RCCL averages in the collective; gloo only sums
-        op = dist.ReduceOp.AVG if nccl else dist.ReduceOp.SUM
-        inv = 1.0 / dist.get_world_size()
-        flat = g_emb.view(-1)
-        n = flat.numel()
-        step = -(-n // self.comm_chunks)
-        step += (-step) % 4                                  # FusedAdam ranges start on multiples of 4 elements
-        bounds = [(lo, min(lo + step, n)) for lo in range(0, n, step)]
-        if self.comm_dtype is None:
-            wire = [flat[lo:hi] for lo, hi in bounds]
-        else:                                                # opt-in: the table gradient crosses xGMI in 16 bits
-            wire = [flat[lo:hi].to(self.comm_dtype) for lo, hi in bounds]
-        works = [dist.all_reduce(t, op=op, async_op=True) for t in wire]
-        w_dw = dist.all_reduce(dw, op=op, async_op=True)
-        if issue_prefetch is not None:
-            issue_prefetch(background=False)                  # marches while the gradients are on the wire
-        for (lo, hi), t, w in zip(bounds, wire, works):
-            w.wait()
-            if self.comm_dtype is not None:
-                flat[lo:hi].copy_(t)
-            if not nccl:
-                flat[lo:hi].mul_(inv)
-            self.opt.step_now(only=[emb], ranges={emb: (lo, hi)}, zero_grads=True)
-        self._cleared_grad = emb.grad                         # every piece cleared by its Adam pass: kept for the next step
-        w_dw.wait()
-        if not nccl:
-            dw.mul_(inv)
-        small = fused_network.network_params(m)[1:]
-        for p, g in zip(small, fused_network.unpack_weight_grads(dw, getattr(m, "out_dim_color", 3),
-                                                                 fused_network.kind_of(m))):
-            p.grad = g.view_as(p)
-        self.opt.step_now(only=small)
-
-    def _owner_range(self):
-        """(lo, hi, world) of this rank's slice of the flat table for the fused sharded tail, or None when that tail does
-        not apply (all-reduce tail, ragged shards, 16-bit wire format, an optimizer without the record-list pass)."""
-        import torch.distributed as dist
-        if not (self.fused_sharded and self.comm_mode == "sharded" and self.comm_dtype is None and self.avg is not None
-                and hasattr(self.opt, "step_grid_table") and not self.use_graphs
-                and dist.is_available() and dist.is_initialized()):
-            return None
-        emb = getattr(getattr(self.model, "encoder", None), "embeddings", None)
-        if emb is None or getattr(self.model.encoder, "level_dim", 0) != 2:
-            return None
-        world, rank = dist.get_world_size(), dist.get_rank()
-        # measurement aid (tools/dp_tail_overhead.py): a one-rank world that OWNS only 1 / N of the table, i.e. pays an
-        # N-rank world's dense route for the other (N - 1) / N (the collectives degenerate; nothing is averaged)
-        pretend = int(getattr(self, "pretend_world", 0) or 0)
-        if pretend > 1 and world == 1:
-            world = pretend
-        n = emb.numel()
-        if n % world or (n // world) % 4:
-            return None
-        shard = n // world
-        return rank * shard, (rank + 1) * shard, world
-
-    def _finish_sharded_fused(self, own, issue_prefetch=None):
-        """The sharded tail with the one-GPU flush kept for this rank's own slice: the backward left the slice's tiles as
-        record lists and made only the rest of the gradient dense (enerf_grid_owner_range); the dense buffer is
-        reduce-scattered in place (SUM: this rank's slice receives the OTHER ranks' share), the optimizer pass sums its own
-        lists in LDS on top of it, divides by the number of ranks, updates the slice and clears the buffer, and the slices
-        are all-gathered in place.  Same update as _finish_sharded up to the order of the fp32 sums."""
-        import torch.distributed as dist
-        from . import _lib as L
-        from . import fused_network
-        m = self.model
-        lo, hi, world = own
-        g_emb, dw = self._raw_grads
-        self._raw_grads = None
-        emb = m.encoder.embeddings
-        if g_emb is None:
-            g_emb = emb.grad
-        else:
-            emb.grad = g_emb
-        nccl = dist.get_backend() == "nccl"
-        flat = g_emb.view(-1)
-        try:
-            w_dw = dist.all_reduce(dw, op=dist.ReduceOp.AVG if nccl else dist.ReduceOp.SUM, async_op=True)
-            # SUM, not AVG: the optimizer pass applies 1 / ranks to dense share + own lists together (and a one-rank world's
-            # in-place SUM is free where RCCL's AVG runs a scaling kernel over the 52 MB)
-            real = dist.get_world_size() == world             # (False: tools/dp_tail_overhead.py's pretend world)
-            if nccl:                                          # in place: slice r of the buffer <- sum of everybody's
-                work = dist.reduce_scatter_tensor(flat[lo:hi], flat if real else flat[lo:hi], op=dist.ReduceOp.SUM,
-                                                  async_op=True)
-            else:                                             # gloo has no reduce-scatter
-                work = dist.all_reduce(flat, op=dist.ReduceOp.SUM, async_op=True)
-            if issue_prefetch is not None:
-                issue_prefetch(background=False)
-            work.wait()
-            w_dw.wait()
-            if not nccl:
-                dw.mul_(1.0 / world)
-            small = fused_network.network_params(m)[1:]
-            for q, g in zip(small, fused_network.unpack_weight_grads(dw, getattr(m, "out_dim_color", 3),
-                                                                     fused_network.kind_of(m))):
-                q.grad = g.view_as(q)
-            enc = m.encoder
-            self.opt.step_grid_table(emb, enc.offsets, enc.level_dim, extra=small)      # (the owner range is still set)
-        finally:
-            L.lib().enerf_grid_owner_range(0, 0, 1.0)
-        self._cleared_grad = emb.grad                         # cleared everywhere by the optimizer pass
-        p = emb.data.view(-1)
-        if nccl:
-            dist.all_gather_into_tensor(p if real else p[lo:hi], p[lo:hi])          # in place: slice r of p <- rank r
-        else:
-            pieces = [torch.empty(hi - lo, dtype=p.dtype, device=p.device) for _ in range(world)]
-            dist.all_gather(pieces, p[lo:hi].contiguous())
-            for r, piece in enumerate(pieces):
-                if r * (hi - lo) != lo:
-                    p[r * (hi - lo):(r + 1) * (hi - lo)].copy_(piece)
+    def _reuse_cleared_grad(self, emb):
+        """Only a buffer the last flush left clean may be added into: -> emb.grad when it is the buffer the last
+        optimizer pass cleared (`_cleared_grad`), else None (the caller drops whatever is there).  The claim is spent
+        either way: whoever clears the buffer next sets `_cleared_grad` again."""
+        keep = emb.grad if (self._cleared_grad is not None and emb.grad is self._cleared_grad) else None
+        self._cleared_grad = None
+        return keep
 
     @staticmethod
     def _discard_pending_records():
@@ -600,187 +481,39 @@ class TrainHarness:
         from . import _lib
         _lib.lib().enerf_grid_records_discard(_lib.stream_handle())
 
-    def _finish_sharded(self, issue_prefetch=None):
-        """The other data-parallel tail (SURVEY.md 8e "scaling risk (b)"): the table gradient is reduce-scattered, every
-        rank runs Adam on its own 1/N of the table only (the 28 B/element optimizer pass shrinks N-fold) and the updated
-        slices are all-gathered into every replica's table.  Same bytes on the wire as the ring all-reduce
-        (2 (N-1)/N x 52 MB), but the gather half moves parameters, which the next step needs only at its first grid
-        encode.  Replicas stay bit-identical: every element is updated by exactly one rank and copied to the others.
-        The MLP gradients (37 KB) keep their all-reduce; their Adam runs everywhere."""
-        import torch.distributed as dist
-        from . import fused_network
-        m = self.model
-        g_emb, dw = self._raw_grads
-        self._raw_grads = None
-        emb = m.encoder.embeddings
-        if g_emb is None:
-            g_emb = emb.grad
-        else:
-            emb.grad = g_emb
-        world, rank = dist.get_world_size(), dist.get_rank()
-        nccl = dist.get_backend() == "nccl"
-        flat = g_emb.view(-1)
-        n = flat.numel()
-        shard = -(-n // world)
-        shard += (-shard) % 4                                 # FusedAdam ranges start on multiples of 4 elements
-        lo, hi = min(rank * shard, n), min((rank + 1) * shard, n)
-        even = shard * world == n
-        w_dw = dist.all_reduce(dw, op=dist.ReduceOp.AVG if nccl else dist.ReduceOp.SUM, async_op=True)
-        if nccl and even:
-            mine = torch.empty(shard, dtype=flat.dtype, device=flat.device)
-            work = dist.reduce_scatter_tensor(mine, flat, op=dist.ReduceOp.AVG, async_op=True)
-        else:                                                 # gloo has no reduce-scatter; ragged tables: all-reduce
-            work = dist.all_reduce(flat, op=dist.ReduceOp.AVG if nccl else dist.ReduceOp.SUM, async_op=True)
-            mine = None
-        if issue_prefetch is not None:
-            issue_prefetch(background=False)
-        work.wait()
-        if mine is not None:
-            flat[lo:hi].copy_(mine)
-        elif not nccl:
-            flat[lo:hi].mul_(1.0 / world)
-        if hi > lo:
-            self.opt.step_now(only=[emb], ranges={emb: (lo, hi)}, zero_grads=True, advance=True)
-        # this rank's local contributions to the other slices are spent: clear them for the next step
-        flat[:lo].zero_()
-        flat[hi:].zero_()
-        self._cleared_grad = emb.grad
-        p = emb.data.view(-1)
-        if even and nccl:
-            gather = dist.all_gather_into_tensor(p, p[lo:hi], async_op=True)       # in place: slice r of p <- rank r
-        else:                                                 # equal-sized (padded) pieces for any backend / ragged table
-            send = torch.zeros(shard, dtype=p.dtype, device=p.device)
-            send[:hi - lo] = p[lo:hi]
-            pieces = [torch.empty(shard, dtype=p.dtype, device=p.device) for _ in range(world)]
-            gather = dist.all_gather(pieces, send, async_op=True)
-        w_dw.wait()
-        if not nccl:
-            dw.mul_(1.0 / world)
-        small = fused_network.network_params(m)[1:]
-        for q, g in zip(small, fused_network.unpack_weight_grads(dw, getattr(m, "out_dim_color", 3),
-                                                                 fused_network.kind_of(m))):
-            q.grad = g.view_as(q)
-        self.opt.step_now(only=small)
-        gather.wait()
-        if not (even and nccl):
-            for r, piece in enumerate(pieces):
-                a, b = min(r * shard, n), min((r + 1) * shard, n)
-                if r != rank and b > a:
-                    p[a:b].copy_(piece[:b - a])
+    def _step_then_tail(self, data_parallel, step, issue_prefetch):
+        """The handoff of both RGB step routes: `step(own)` renders and runs the backward; with `data_parallel`,
+        dp_tail.finish then averages the gradients and takes the optimizer step (`issue_prefetch`: the next batch's
+        march, where the tail is to place it).  `own`: this rank's slice of the table where the fused sharded tail
+        applies, set in the library for both and cleared however they end.  A step that raises leaves no record lists."""
+        own = dp_tail.owner_range(self) if data_parallel else None
+        if own is not None:
+            from . import _lib as L
+            L.check(L.lib().enerf_grid_owner_range(own[0], own[1], 1.0 / own[2]), "grid_owner_range")
+        try:
+            try:
+                out = step(own)
+            except BaseException:
+                self._discard_pending_records()
+                raise
+            if data_parallel:
+                dp_tail.finish(self, own, issue_prefetch)
+        finally:
+            if own is not None:
+                L.lib().enerf_grid_owner_range(0, 0, 1.0)
+        return out
 
     def gather_sharded_optimizer_state(self):
-        """After steps taken with the sharded tail every rank holds current Adam moments only for its own slice of the
-        table.  Before anything that needs them whole -- switching back to the all-reduce tail, saving a checkpoint --
-        the slices are all-gathered (2 x 52 MB, once)."""
-        import torch.distributed as dist
-        emb = getattr(getattr(self.model, "encoder", None), "embeddings", None)
-        opt = getattr(self, "opt", None)
-        st = opt.state.get(emb) if emb is not None and opt is not None else None
-        if not st or not (dist.is_available() and dist.is_initialized()) or dist.get_world_size() == 1:
-            return
-        world, rank = dist.get_world_size(), dist.get_rank()
-        n = emb.numel()
-        shard = -(-n // world)
-        shard += (-shard) % 4
-        lo, hi = min(rank * shard, n), min((rank + 1) * shard, n)
-        for key in ("exp_avg", "exp_avg_sq"):
-            flat = st[key].view(-1)
-            send = torch.zeros(shard, dtype=flat.dtype, device=flat.device)
-            send[:hi - lo] = flat[lo:hi]
-            pieces = [torch.empty(shard, dtype=flat.dtype, device=flat.device) for _ in range(world)]
-            dist.all_gather(pieces, send)
-            for r, piece in enumerate(pieces):
-                a, b = min(r * shard, n), min((r + 1) * shard, n)
-                if r != rank and b > a:
-                    flat[a:b].copy_(piece[:b - a])
+        """Data parallel, after steps with a sharded tail: the table's Adam moments, whole on every rank again."""
+        dp_tail.gather_sharded_optimizer_state(self)
 
     def tune_comm(self, step_fn, candidates=(1, 2, 4, 8), window=None):
-        """Data parallel: pick `comm_chunks` by measurement.  How the table-gradient all-reduce is best cut depends on
-        the link topology and the number of ranks (per-collective latency against Adam / collective overlap), so each
-        candidate runs `window` steps of `step_fn(i)` -- one update_extra_state period, so every window holds the same
-        work -- timed between device synchronisations; the slowest rank's time decides (MAX all-reduce, hence the same
-        choice on every rank).  -> {chunks: ms_per_step}, {} when there is nothing to tune."""
-        import time
-        import torch.distributed as dist
-        if self.avg is None or not (dist.is_available() and dist.is_initialized()) or dist.get_world_size() == 1:
-            return {}
-        window = int(window or self.update_interval)
-        dev = next(self.model.parameters()).device
-        sync = (lambda: torch.cuda.synchronize(dev)) if dev.type == "cuda" else (lambda: None)
-        i = 0
-        timings = {}
-        self.comm_mode = "allreduce"
-        for n, c in enumerate((candidates[0],) + tuple(candidates)):       # the first window only warms up
-            self.comm_chunks = int(c)
-            sync()
-            dist.barrier()
-            t0 = time.perf_counter()
-            for _ in range(window):
-                step_fn(i)
-                i += 1
-            sync()
-            dt = torch.tensor([time.perf_counter() - t0], dtype=torch.float64, device=dev)
-            dist.all_reduce(dt, op=dist.ReduceOp.MAX)
-            if n:
-                timings[int(c)] = float(dt.item()) / window * 1e3
-        self.comm_chunks = min(timings, key=timings.get)
-        # the other tail: reduce-scatter -> Adam on this rank's slice -> all-gather (two windows: the first warms up)
-        self.comm_mode = "sharded"
-        sharded_ms = None
-        for n in range(2):
-            sync()
-            dist.barrier()
-            t0 = time.perf_counter()
-            for _ in range(window):
-                step_fn(i)
-                i += 1
-            sync()
-            dt = torch.tensor([time.perf_counter() - t0], dtype=torch.float64, device=dev)
-            dist.all_reduce(dt, op=dist.ReduceOp.MAX)
-            sharded_ms = float(dt.item()) / window * 1e3
-        self.gather_sharded_optimizer_state()                 # whichever tail runs next starts from whole moments
-        self.comm_mode = "sharded" if sharded_ms < timings[self.comm_chunks] else "allreduce"
-        # with the cut settled: where the next batch's march is issued (beside the backward, or beside the collectives)
-        placements = {}
-        for at in ("forward", "mlp_backward", "collectives"):
-            self.prefetch_at = at
-            sync()
-            dist.barrier()
-            t0 = time.perf_counter()
-            for _ in range(window):
-                step_fn(i)
-                i += 1
-            sync()
-            dt = torch.tensor([time.perf_counter() - t0], dtype=torch.float64, device=dev)
-            dist.all_reduce(dt, op=dist.ReduceOp.MAX)
-            placements[at] = float(dt.item()) / window * 1e3
-        self.prefetch_at = min(placements, key=placements.get)
-        self.tuned = {"chunks_ms_per_step": dict(timings), "sharded_ms_per_step": sharded_ms,
-                      "mode": self.comm_mode, "prefetch_at_ms_per_step": placements}
-        return timings
+        """Data parallel: pick `comm_chunks`, `comm_mode` and `prefetch_at` by measurement -> {chunks: ms_per_step}."""
+        return dp_tail.tune_comm(self, step_fn, candidates, window)
 
     def probe_comm_dtype(self, step_fn, dtype=torch.bfloat16, window=None, first_step=0):
-        """Data parallel: ms per step over one window with the table gradient on the wire in `dtype` (the opt-in
-        `comm_dtype`), for reporting next to the fp32 figure; the setting itself is restored.  None on one rank."""
-        import time
-        import torch.distributed as dist
-        if self.avg is None or not (dist.is_available() and dist.is_initialized()) or dist.get_world_size() == 1:
-            return None
-        window = int(window or self.update_interval)
-        dev = next(self.model.parameters()).device
-        keep, self.comm_dtype = self.comm_dtype, dtype
-        try:
-            torch.cuda.synchronize(dev)
-            dist.barrier()
-            t0 = time.perf_counter()
-            for i in range(first_step, first_step + window):
-                step_fn(i)
-            torch.cuda.synchronize(dev)
-            dt = torch.tensor([time.perf_counter() - t0], dtype=torch.float64, device=dev)
-            dist.all_reduce(dt, op=dist.ReduceOp.MAX)
-        finally:
-            self.comm_dtype = keep
-        return float(dt.item()) / window * 1e3
+        """Data parallel: ms per step over one window with the table gradient on the wire in `dtype`; None on one rank."""
+        return dp_tail.probe_comm_dtype(self, step_fn, dtype, window, first_step)
 
     def _loss_slot(self):
         """Loss values land in a ring of device scalars, cleared once per lap: no loss kernels, no per-step fill (laps are
@@ -808,14 +541,13 @@ class TrainHarness:
     def _step_rgb_native(self, rays_o, rays_d, target, next_rays, data_parallel=False, checked=False):
         """The steady-state step as one library call (fused_render.train_step_native -> enerf_train_step_mse): the same
         launches in the same order as _step_rgb_manual's one-GPU route, issued from C.  data_parallel: the call stops
-        after the table's backward (dense gradient, no optimizer) and one of the data-parallel tails takes over -- the
-        native one (two more library calls) when the library has its communicator."""
+        after the table's backward (dense gradient, no optimizer) and one of the data-parallel tails takes over
+        (dp_tail.finish)."""
         from . import fused_render
         m = self.model
         emb = m._modules["encoder"]._parameters["embeddings"]
-        if not (self._cleared_grad is not None and emb.grad is self._cleared_grad):
-            emb.grad = None                     # only a buffer the last flush left clean may be added into
-        self._cleared_grad = None
+        if self._reuse_cleared_grad(emb) is None:
+            emb.grad = None
         if not checked:                         # (decided by the full checks: later steps of the same signature skip them)
             self._native_route_sig, self._native_route_dp = self._pending_sig, data_parallel
         nxt = None
@@ -832,28 +564,16 @@ class TrainHarness:
             # stream, the ring of step counters is copied out here, a whole step before the update wants the budget
             fused_render.stage_ring_copy(m)
         loss = self._loss_slot()
-        own = self._owner_range() if data_parallel else None
-        if own is not None:
-            from . import _lib as L
-            L.check(L.lib().enerf_grid_owner_range(own[0], own[1], 1.0 / own[2]), "grid_owner_range")
-        try:
+
+        def step(own):                          # (no march for the tail to place: it is queued behind the MLP backward)
             out = fused_render.train_step_native(m, rays_o, rays_d, target, self.opt, next_rays=nxt,
                                                  side_stream=self._side, loss_out=loss, perturb=self.perturb,
                                                  raw=data_parallel, defer_dp=own is not None)
-        except BaseException:
-            if own is not None:
-                L.lib().enerf_grid_owner_range(0, 0, 1.0)
-            self._discard_pending_records()
-            raise
-        if data_parallel:
-            self._raw_grads = (None, out[1])            # (the table's gradient sits in embeddings.grad)
-            if own is not None:
-                self._finish_sharded_fused(own, None)
-                return loss
-            tail = self._finish_sharded if self.comm_mode == "sharded" else self._finish_distributed
-            tail(None)                                  # the next batch's march is already queued (behind the MLP backward)
-            return loss
-        self._cleared_grad = emb.grad
+            if data_parallel:
+                self._raw_grads = (None, out[1])        # (the table's gradient sits in embeddings.grad)
+        self._step_then_tail(data_parallel, step, None)
+        if not data_parallel:
+            self._cleared_grad = emb.grad
         return loss
 
     def _step_rgb_manual(self, rays_o, rays_d, target, next_rays, **render_kw):
@@ -872,27 +592,15 @@ class TrainHarness:
         # optimizer's pass over the table sums them tile by tile in LDS (FusedAdam.step_grid_table)
         fuse_table = (self.fuse_table_adam and self.avg is None and hasattr(self.opt, "step_grid_table")
                       and not self.use_graphs)
-        own = self._owner_range() if chunked else None
-        if own is not None:
-            from . import _lib as L
-            L.check(L.lib().enerf_grid_owner_range(own[0], own[1], 1.0 / own[2]), "grid_owner_range")
-        try:
-            tail_side = side if (not late and self.prefetch_at == "mlp_backward") else None
-            loss = self._manual_fwd_bwd(rays_o, rays_d, target,
+        tail_side = side if (not late and self.prefetch_at == "mlp_backward") else None
+
+        def step(own):
+            return self._manual_fwd_bwd(rays_o, rays_d, target,
                                         after_forward=None if (late or tail_side is not None) else side, raw=chunked,
                                         defer_table=fuse_table or own is not None, after_mlp_backward=tail_side,
                                         **render_kw)
-        except BaseException:
-            if own is not None:
-                L.lib().enerf_grid_owner_range(0, 0, 1.0)
-            self._discard_pending_records()
-            raise
+        loss = self._step_then_tail(chunked, step, side if late else None)
         if chunked:
-            if own is not None:
-                self._finish_sharded_fused(own, side if late else None)
-                return loss
-            tail = self._finish_sharded if self.comm_mode == "sharded" else self._finish_distributed
-            tail(side if late else None)
             return loss
         self._reduce_grads(None if side is not None else next_rays)
         if fuse_table:
@@ -1135,9 +843,8 @@ class TrainHarness:
             fuse_table = (self.fuse_table_adam and self.avg is None and hasattr(self.opt, "step_grid_table")
                           and not self.use_graphs)
             emb = self.model.encoder.embeddings
-            if emb.grad is not self._cleared_grad:          # only a buffer the last flush left clean may be added into
+            if self._reuse_cleared_grad(emb) is None:
                 emb.grad = None
-            self._cleared_grad = None
             try:
                 tail = self.prefetch_at == "mlp_backward"
                 loss, _ = train_step_events_manual(self.model, data, opt, after_forward=None if tail else side,
@@ -1167,9 +874,8 @@ class TrainHarness:
         from . import fused_render
         m = self.model
         emb = m._modules["encoder"]._parameters["embeddings"]
-        if not (self._cleared_grad is not None and emb.grad is self._cleared_grad):
-            emb.grad = None                     # only a buffer the last flush left clean may be added into
-        self._cleared_grad = None
+        if self._reuse_cleared_grad(emb) is None:
+            emb.grad = None
         nxt = None
         if (next_data is not None and self.prefetch and self.global_step % self.update_interval != 0
                 and all(fused_render.supported(m, next_data[o].contiguous().view(-1, 3),

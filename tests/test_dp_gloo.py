@@ -225,7 +225,7 @@ def _tail_worker(rank, world, port, n_rays, mode, outdir):
     sys.path.insert(0, ROOT)
     torch.set_num_threads(2)
     _inject_oracle()
-    from enerf_amd import parallel
+    from enerf_amd import dp_tail, parallel
     from enerf_amd.optim import FusedAdam
     from enerf_amd.trainer import TrainHarness
     parallel.init_from_env(backend="gloo")
@@ -241,7 +241,7 @@ def _tail_worker(rank, world, port, n_rays, mode, outdir):
         (((out["image"] - target[:, lo:hi]) ** 2).sum() * (world / (3.0 * n_rays))).backward()
         # hand the tail what the closed-form step hands it: (table gradient, flat MLP dW)
         h._raw_grads = (m.encoder.embeddings.grad, _pack_dw(m))
-        (h._finish_sharded if mode == "sharded" else h._finish_distributed)()
+        assert dp_tail.finish(h, None) == mode
     torch.save({k: v.clone() for k, v in m.state_dict().items()}, os.path.join(outdir, f"tail_{mode}_{rank}.pt"))
     dist.barrier()
     dist.destroy_process_group()
@@ -250,7 +250,7 @@ def _tail_worker(rank, world, port, n_rays, mode, outdir):
 @pytest.mark.timeout(900)
 @pytest.mark.parametrize("mode", ["allreduce", "sharded"])
 def test_two_rank_closed_form_tails_equal_single_process_adam(tmp_path, mode):
-    """TrainHarness._finish_distributed (table gradient all-reduced in 3 pieces, Adam per piece) and _finish_sharded
+    """dp_tail.finish through allreduce_tail (table gradient all-reduced in 3 pieces, Adam per piece) and sharded_tail
     (reduce-scatter -> Adam on the rank's slice -> all-gather) on 2 real ranks over gloo: replicas identical, and equal
     to one process stepping the full batch (the oracle backend computes the gradients; the tails are what is tested)."""
     n_rays, world = 40, 2
@@ -275,3 +275,119 @@ def test_two_rank_closed_form_tails_equal_single_process_adam(tmp_path, mode):
         import importlib
         import enerf_amd.raymarching as rm, enerf_amd.gridencoder as ge, enerf_amd.shencoder as sh
         importlib.reload(rm); importlib.reload(ge); importlib.reload(sh)
+
+
+def test_table_slice_partitions_on_multiples_of_4_and_contains_the_owner_range():
+    """dp_tail.table_slice, the one statement of the slice geometry: the slices are contiguous, disjoint and cover
+    [0, n); every slice that holds anything starts on a multiple of 4; a slice is short or empty only where n is
+    exhausted; and wherever the fused
+    sharded tail's owner range applies (n % world == 0, (n // world) % 4 == 0) it is the exact division."""
+    from enerf_amd.dp_tail import table_slice
+    for n in (4, 6, 4096, 65536, 65538):
+        for w in (1, 2, 3, 8):
+            spans = [table_slice(n, r, w) for r in range(w)]
+            shard = spans[0][2]
+            assert shard % 4 == 0 and shard * w >= n and all(s[2] == shard for s in spans)
+            assert spans[0][0] == 0 and spans[-1][1] == n, (n, w)
+            for r, (lo, hi, _) in enumerate(spans):
+                # (an empty slice is clipped to [n, n): n = 6 puts it at 6, and no optimizer range starts there)
+                assert (lo % 4 == 0 or lo == hi == n) and 0 <= lo <= hi <= n, (n, w, r)
+                if r + 1 < w:
+                    assert hi == spans[r + 1][0], (n, w, r)             # contiguous, hence disjoint
+                assert hi - lo == shard or hi == n, (n, w, r)           # short or empty only once n is exhausted
+            if n % w == 0 and (n // w) % 4 == 0:
+                assert shard * w == n
+                assert [s[:2] for s in spans] == [(r * n // w, (r + 1) * n // w) for r in range(w)], (n, w)
+
+
+def _gather_worker(rank, world, port, outdir):
+    os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), RANK=str(rank), WORLD_SIZE=str(world))
+    sys.path.insert(0, ROOT)
+    from enerf_amd import dp_tail
+    dist.init_process_group("gloo", rank=rank, world_size=world)
+    try:
+        got = {}
+        for n in (64, 70):
+            for async_op in (False, True):
+                lo, hi, shard = dp_tail.table_slice(n, rank, world)
+                v = torch.full((n,), -1.0)                  # the sentinel: what this rank does not own
+                v[lo:hi] = rank + 1
+                handle = dp_tail.gather_slices(v, lo, hi, shard, world, rank, in_place_ok=False, async_op=async_op)
+                handle.wait()
+                got[(n, async_op)] = v
+        torch.save(got, os.path.join(outdir, f"gather{rank}.pt"))
+    finally:
+        dist.destroy_process_group()
+
+
+def test_gather_slices_even_and_ragged_sync_and_async(tmp_path):
+    """dp_tail.gather_slices over gloo, world_size 2: each rank fills its own slice of a vector with rank + 1; after the
+    gather both ranks hold the same vector, every element owned by rank r equal to r + 1 -- for an even length and a
+    ragged one (70: shards of 36, rank 1's slice clipped to 34), synchronous and with async_op."""
+    from enerf_amd.dp_tail import table_slice
+    world = 2
+    mp.spawn(_gather_worker, args=(world, _free_port(), str(tmp_path)), nprocs=world, join=True)
+    a, b = (torch.load(os.path.join(str(tmp_path), f"gather{r}.pt")) for r in (0, 1))
+    assert set(a) == set(b) == {(64, False), (64, True), (70, False), (70, True)}
+    assert table_slice(70, 1, world) == (36, 70, 36)
+    for (n, async_op), v in a.items():
+        want = torch.empty(n)
+        for r in range(world):
+            lo, hi, _ = table_slice(n, r, world)
+            want[lo:hi] = r + 1
+        assert torch.equal(v, want) and torch.equal(b[(n, async_op)], want), (n, async_op)
+
+
+@pytest.mark.parametrize("own", [(0, 8, 2), None])
+def test_step_to_tail_handoff_clears_the_owner_range_and_discards_records(monkeypatch, own):
+    """TrainHarness._step_then_tail with the library and the tail replaced by recorders: the owner range is set before
+    the step and cleared after the tail, also when either raises; a step that raises has its record lists discarded
+    (with and without an owner range), a tail that raises has not; the exception propagates unchanged; the tail runs
+    once, with the range and the march placement it was handed."""
+    from enerf_amd import _lib, dp_tail
+    from enerf_amd.trainer import TrainHarness
+    calls = []
+
+    class Lib:
+        def enerf_grid_owner_range(self, lo, hi, scale):
+            calls.append(("range", lo, hi, scale))
+            return 0
+
+        def enerf_grid_records_discard(self, stream):
+            calls.append(("discard",))
+    monkeypatch.setattr(_lib, "lib", lambda: Lib())
+    monkeypatch.setattr(_lib, "check", lambda rc, what: None)
+    monkeypatch.setattr(_lib, "stream_handle", lambda: None)
+    monkeypatch.setattr(dp_tail, "owner_range", lambda h: own)
+    h = object.__new__(TrainHarness)
+    setup = [("range", 0, 8, 0.5)] if own else []
+    clear = [("range", 0, 0, 1.0)] if own else []
+    boom = KeyboardInterrupt("boom")            # (BaseException: an interrupted step must clean up too)
+
+    def tail(harness, got_own, prefetch):
+        calls.append(("tail", harness is h, got_own, prefetch))
+        if prefetch == "raise":
+            raise boom
+
+    def step(got_own):
+        calls.append(("step", got_own))
+        return "loss"
+
+    def bad_step(got_own):
+        raise boom
+    monkeypatch.setattr(dp_tail, "finish", tail)
+    assert h._step_then_tail(True, step, "march") == "loss"
+    assert calls == setup + [("step", own), ("tail", True, own, "march")] + clear
+    del calls[:]
+    with pytest.raises(KeyboardInterrupt) as e:
+        h._step_then_tail(True, bad_step, None)
+    assert e.value is boom and calls == setup + [("discard",)] + clear
+    del calls[:]
+    with pytest.raises(KeyboardInterrupt) as e:
+        h._step_then_tail(True, step, "raise")
+    assert e.value is boom and calls == setup + [("step", own), ("tail", True, own, "raise")] + clear
+    del calls[:]
+    assert h._step_then_tail(False, step, None) == "loss" and calls == [("step", None)]      # one GPU: no tail
+    with pytest.raises(KeyboardInterrupt):
+        h._step_then_tail(False, bad_step, None)
+    assert calls == [("step", None), ("discard",)]

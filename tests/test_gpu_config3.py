@@ -2,9 +2,9 @@
 all-reduce of the hash-grid / MLP gradients) at its PER-RANK shape on the one GPU a test box has:
 
   * 8192 rays through both data-parallel tails (chunked all-reduce + Adam per piece; reduce-scatter -> Adam on the slice
-    -> all-gather), each driven natively (`_finish_native`: csrc/dp_tail.hip on the library's own RCCL communicator) and
-    through torch.distributed (`_finish_distributed` / `_finish_sharded`), on the real backend (RCCL) with a world of
-    one rank, against the single-process step (which takes the fused record-list optimizer instead);
+    -> all-gather, with and without the rank's own slice kept as record lists), driven through torch.distributed
+    (enerf_amd/dp_tail.py: `allreduce_tail` / `sharded_tail` / `sharded_fused_tail`), on the real backend (RCCL) with a
+    world of one rank, against the single-process step (which takes the fused record-list optimizer instead);
   * 2 ranks x 8192 rays (gloo, both ranks on this device) against the single-process 16 384-ray step: per-step sample /
     ray counters add up bit for bit, the losses average to the whole batch's loss, the post-Adam parameters agree and
     an evaluation render of the replicas gives the single-process image.  The jitter of a training march is seeded by
@@ -129,15 +129,15 @@ def _gloo_worker(rank, world, port, mode, cold_steps, more_steps, out):
         h.perturb = False
         h.comm_mode = "sharded" if mode.startswith("sharded") else mode
         h.fused_sharded = mode != "sharded_dense"         # "sharded": this rank's slice keeps its record lists (OwnerRange)
-        seen = []
-        if mode == "sharded":
-            inner = h._finish_sharded_fused
-            h._finish_sharded_fused = lambda *a, **k: (seen.append(1), inner(*a, **k))[1]
+        from enerf_amd import dp_tail
+        seen, inner = [], dp_tail.finish                    # (this process's own copy of the module: nothing to restore)
+        dp_tail.finish = lambda *a, **k: (seen.append(inner(*a, **k)), seen[-1])[1]
         l0, c0 = _run(h, data, cold_steps)
         p0, img0 = _params(model), _eval_image(model)
         l1, c1 = _run(h, data, more_steps, first=cold_steps)
-        if mode == "sharded":
-            assert len(seen) == cold_steps + more_steps, len(seen)      # every step went through the fused sharded tail
+        # every step went through the tail its mode names ("sharded": the fused sharded tail)
+        tail = {"sharded": "sharded_fused", "sharded_dense": "sharded"}.get(mode, mode)
+        assert seen == [tail] * (cold_steps + more_steps), seen
         out[(mode, rank)] = (l0, c0, p0, img0, l1, c1, _params(model), int(model.mean_count))
     finally:
         dist.destroy_process_group()

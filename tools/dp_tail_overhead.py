@@ -35,7 +35,7 @@ def main():
     dev = torch.device("cuda", 0)
     batches = bench.build_batches(8, a.rays, dev, 0, a.bound)
     # ("sharded, own slice fused": the default sharded tail -- this rank's slice of the table keeps its record lists for
-    #  the optimizer pass, TrainHarness._finish_sharded_fused; "dense": every tile made dense first, _finish_sharded)
+    #  the optimizer pass, dp_tail.sharded_fused_tail; "dense": every tile made dense first, dp_tail.sharded_tail)
     # (last column: pretend_world -- this one rank owns 1 / N of the table and pays an N-rank world's dense route for the
     #  rest: what a rank of N = 8 does between its backward and its optimizer pass, minus the wire)
     configs = (("single process", 1, 4, None, None, "allreduce", True, 0),
