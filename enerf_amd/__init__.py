@@ -12,3 +12,14 @@ Layout
 There is no CPU fallback in this package: every hot-path call goes to libenerf_hip.so or raises.
 """
 __version__ = "0.1.0"
+
+# the two data-side entry points, resolved on first use (importing the package stays free of torch)
+_EXPORTS = {"FrameSampler": "frame_sampler", "EventSampler": "event_sampler"}
+__all__ = sorted(_EXPORTS)
+
+
+def __getattr__(name):
+    if name in _EXPORTS:
+        import importlib
+        return getattr(importlib.import_module("." + _EXPORTS[name], __name__), name)
+    raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

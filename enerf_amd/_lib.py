@@ -97,6 +97,10 @@ SIGNATURES = {
     "enerf_event_loss_fwd_bwd": [_vp, _vp, _vp, _u32, _u32, _u32, _f32, _f32, _f32, _vp, _vp, _vp, _vp, _vp],
     "enerf_event_pair_rays": [_vp, _vp, _vp, _vp, _u32, _vp, _vp, _u32, _u32, _vp, _vp, _vp, _vp, _u32, _f32, _f32, _f32,
                               _f32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
+    "enerf_event_single_pair_rays": [_vp, _u32, _vp, _vp, _u32, _vp, _vp, _u32, _vp, _vp, _vp, _vp, _u32, _f32, _f32, _f32,
+                                     _f32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
+    "enerf_no_event_rays": [_vp, _u32, _vp, _vp, _u32, _c.c_double, _c.c_double, _vp, _vp, _vp, _vp, _u32, _f32, _f32,
+                            _f32, _f32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
     "enerf_occupied_box_update": [_vp, _u32, _u32, _f32, _vp],
     "enerf_debug_mlp32_fused_backward": [_int],
     "enerf_mlp32_precision": [_int],

@@ -31,7 +31,7 @@ EXTRA = {"ffmlp.hip": _VGPR_FORM, "mlp32s.hip": _VGPR_FORM, "mlp32s_f16.hip": _V
 FLAGS += os.environ.get("ENERF_DEFINES", "").split()
 HEADERS = [os.path.join(CSRC, "common.h"), os.path.join(CSRC, "ffmlp_common.h"), os.path.join(CSRC, "mlp32_common.h"), os.path.join(CSRC, "mlp32s_ops.h"), os.path.join(CSRC, "mfma_guard.h"),
            os.path.join(CSRC, "sh_basis.h"), os.path.join(CSRC, "march_lattice.h"), os.path.join(CSRC, "sweep_points.h"),
-           os.path.join(CSRC, "mc_tables.h"),
+           os.path.join(CSRC, "mc_tables.h"), os.path.join(CSRC, "pose_track.h"),
            os.path.join(_HERE, "..", "include", "enerf_hip.h")]
 
 

@@ -2,71 +2,17 @@
 // (nerf/provider.py:1364-1441):
 //   accumulate_evs branch (:1367-1398): drawn event -> step back if it is the last at its pixel -> window end among
 //     its next min(num_successor, acc_max_num_evs + 1) events -> polarity sum over the window (prefix sums);
-//   "computing poses online" branch (:1411-1420): camera pose at the two event times from the pose track -- rotation by
-//     scipy's Slerp (R_i * exp(alpha * log(R_i^T R_{i+1}))), translation by interp1d(kind="cubic") -- evaluated here
-//     from per-segment tables prepared once (enerf_amd/pose_interp.py), in double like scipy, then rounded to fp32 as
-//     `torch.Tensor(get_hom_trafos(...))` does;
-//   get_event_rays (nerf/utils.py:184-216): pixel -> unit camera direction -> world direction / origin at both poses.
+//   accumulate_evs off (:1400-1405, what every shipped config trains with): per chosen pixel the drawn event that has a
+//     successor and that successor, the successor's polarity (k_event_single_pair_rays);
+//   --negative_event_sampling (:1443-1476): pixels of a chunk where nothing happened, two ordered times (k_no_event_rays);
+//   "computing poses online" (:1411-1420) and get_event_rays (nerf/utils.py:184-216) for all three: pose_track.h.
 // One thread per pair; everything a pair needs is 2 table rows + 2 track segments.
 #include "common.h"
+#include "pose_track.h"
+
+using namespace enerf;
 
 namespace {
-
-struct Intr {
-    float fx, fy, cx, cy;
-};
-
-// index of the track segment [knots[i], knots[i+1]] holding t (last segment for t == knots[K-1]); -1 outside the track
-__device__ __forceinline__ int find_segment(const double* __restrict__ knots, uint32_t K, double t) {
-    if (!(t >= knots[0]) || !(t <= knots[K - 1])) return -1;
-    uint32_t lo = 0, hi = K - 1;                      // invariant: knots[lo] <= t <= knots[hi]
-    while (hi - lo > 1) {
-        const uint32_t mid = (lo + hi) >> 1;
-        if (knots[mid] <= t) lo = mid; else hi = mid;
-    }
-    return (int)lo;
-}
-
-// c2w[3][4] (fp32) at time t
-__device__ __forceinline__ bool pose_at(const double* __restrict__ knots, const double* __restrict__ rot,
-                                        const double* __restrict__ rotvec, const double* __restrict__ tcoef, uint32_t K,
-                                        double t, float (&m)[3][4]) {
-    const int s = find_segment(knots, K, t);
-    if (s < 0) return false;
-    const double h = knots[s + 1] - knots[s];
-    const double alpha = (t - knots[s]) / h;
-    // Rodrigues: exp(alpha * w)
-    const double wx = alpha * rotvec[s * 3], wy = alpha * rotvec[s * 3 + 1], wz = alpha * rotvec[s * 3 + 2];
-    const double th2 = wx * wx + wy * wy + wz * wz;
-    const double th = sqrt(th2);
-    double a, b;                                      // exp = I + a [w]x + b [w]x^2
-    if (th < 1e-6) {
-        a = 1.0 - th2 / 6.0;
-        b = 0.5 - th2 / 24.0;
-    } else {
-        a = sin(th) / th;
-        b = (1.0 - cos(th)) / th2;
-    }
-    double E[3][3];
-    E[0][0] = 1.0 - b * (wy * wy + wz * wz); E[0][1] = -a * wz + b * wx * wy;        E[0][2] = a * wy + b * wx * wz;
-    E[1][0] = a * wz + b * wx * wy;          E[1][1] = 1.0 - b * (wx * wx + wz * wz); E[1][2] = -a * wx + b * wy * wz;
-    E[2][0] = -a * wy + b * wx * wz;         E[2][1] = a * wx + b * wy * wz;          E[2][2] = 1.0 - b * (wx * wx + wy * wy);
-    const double* R = rot + (size_t)s * 9;
-    for (int i = 0; i < 3; i++)
-        for (int j = 0; j < 3; j++)
-            m[i][j] = (float)(R[i * 3] * E[0][j] + R[i * 3 + 1] * E[1][j] + R[i * 3 + 2] * E[2][j]);
-    // translation: cubic in (t - knots[s]), coefficients highest power first: tcoef[s][k][axis]
-    const double u = t - knots[s];
-    const double* c = tcoef + (size_t)s * 12;
-    for (int ax = 0; ax < 3; ax++) m[ax][3] = (float)(((c[ax] * u + c[3 + ax]) * u + c[6 + ax]) * u + c[9 + ax]);
-    return true;
-}
-
-__device__ __forceinline__ void ray_of(const float (&m)[3][4], float dx, float dy, float dz, float* o, float* d) {
-    o[0] = m[0][3]; o[1] = m[1][3]; o[2] = m[2][3];
-    // torch.sum(dirs_cams[..., None, :] * c2w[..., :3, :3], axis=-1): products rounded, then summed left to right
-    for (int i = 0; i < 3; i++) d[i] = (dx * m[i][0] + dy * m[i][1]) + dz * m[i][2];
-}
 
 __global__ void __launch_bounds__(256) k_event_pair_rays(
     const float* __restrict__ events, const uint8_t* __restrict__ no_successor, const int64_t* __restrict__ num_successor,
@@ -88,16 +34,104 @@ __global__ void __launch_bounds__(256) k_event_pair_rays(
     end_out[k] = e;
     pols[k] = (float)(pol_cumsum[e + 1] - pol_cumsum[s + 1]);
     const float x = events[(size_t)s * 4], y = events[(size_t)s * 4 + 1];
-    // camera direction (get_event_rays): fp32, z = 1
-    const float us = (x - in.cx) / in.fx, vs = (y - in.cy) / in.fy;
-    const float nrm = sqrtf((us * us + vs * vs) + 1.0f);
-    const float dx = us / nrm, dy = vs / nrm, dz = 1.0f / nrm;
+    float dx, dy, dz;
+    cam_dir(in, x, y, dx, dy, dz);
     float m[3][4];
     const bool ok1 = pose_at(knots, rot, rotvec, tcoef, K, (double)events[(size_t)s * 4 + 2], m);
     ray_of(m, dx, dy, dz, o1 + (size_t)k * 3, d1 + (size_t)k * 3);
     const bool ok2 = pose_at(knots, rot, rotvec, tcoef, K, (double)events[(size_t)e * 4 + 2], m);
     ray_of(m, dx, dy, dz, o2 + (size_t)k * 3, d2 + (size_t)k * 3);
     if (!(ok1 && ok2)) atomicAdd(outside, 1);                        // interp1d(bounds_error=True) would raise
+}
+
+// a pair (or pixel) whose index is not one: nothing is read for it, its rays are zero
+__device__ __forceinline__ void zero_rays(uint32_t k, float* __restrict__ o1, float* __restrict__ d1,
+                                          float* __restrict__ o2, float* __restrict__ d2) {
+    const size_t r = (size_t)k * 3;
+    for (int a = 0; a < 3; a++) o1[r + a] = d1[r + a] = o2[r + a] = d2[r + a] = 0.0f;
+}
+
+// the rays of pixel (x, y) through the camera at t1 and at t2 (track units); false when a time lies outside the track
+__device__ __forceinline__ bool ray_pair(const double* __restrict__ knots, const double* __restrict__ rot,
+                                         const double* __restrict__ rotvec, const double* __restrict__ tcoef, uint32_t K,
+                                         const Intr& in, float x, float y, double t1, double t2, uint32_t k,
+                                         float* __restrict__ o1, float* __restrict__ d1, float* __restrict__ o2,
+                                         float* __restrict__ d2) {
+    float dx, dy, dz;
+    cam_dir(in, x, y, dx, dy, dz);
+    bool ok = true;
+    const double ts[2] = {t1, t2};
+    float* const os[2] = {o1, o2};
+    float* const ds[2] = {d1, d2};
+    for (int j = 0; j < 2; j++) {
+        float m[3][4] = {};                                          // (outside the track: a zero pose, counted)
+        ok = pose_at(knots, rot, rotvec, tcoef, K, ts[j], m) && ok;
+        ray_of(m, dx, dy, dz, os[j] + (size_t)k * 3, ds[j] + (size_t)k * 3);
+    }
+    return ok;
+}
+
+// accumulate_evs off (provider.py:1400-1405): per pixel the drawn event that has a successor,
+// (np.random.rand(P) * num - 1).astype(int) + first; pair k is that event of pixel choice[k] and its direct successor.
+__global__ void __launch_bounds__(256) k_event_single_pair_rays(
+    const float* __restrict__ events, uint32_t N, const int64_t* __restrict__ num_at_xy,
+    const int64_t* __restrict__ first_at_xy, uint32_t P, const double* __restrict__ u_xy,
+    const int64_t* __restrict__ choice, uint32_t M, const double* __restrict__ knots, const double* __restrict__ rot,
+    const double* __restrict__ rotvec, const double* __restrict__ tcoef, uint32_t K, Intr in, float* __restrict__ o1,
+    float* __restrict__ d1, float* __restrict__ o2, float* __restrict__ d2, float* __restrict__ pols,
+    int64_t* __restrict__ start_out, int64_t* __restrict__ end_out, int* __restrict__ outside, int* __restrict__ bad) {
+    const uint32_t k = blockIdx.x * blockDim.x + threadIdx.x;
+    if (k >= M) return;
+    const int64_t c = choice[k];
+    int64_t s = -1;
+    if (c >= 0 && c < (int64_t)P) {
+        const double v = u_xy[c] * (double)num_at_xy[c] - 1.0;      // product and difference each rounded (no contraction)
+        // the cast truncates toward zero: (-1, 0) -> 0.  (u_xy == 0 exactly gives -1 as in the reference: the event
+        // before the pixel's first; for pixel 0 that is no event and is counted below.  NaN / huge: not cast.)
+        if (v >= -1.0 && v < 4294967296.0) s = (int64_t)v + first_at_xy[c];
+    }
+    if (s < 0 || s > (int64_t)N - 2) {                               // not a pixel (or tables that are none): no read
+        zero_rays(k, o1, d1, o2, d2);
+        pols[k] = 0.0f;
+        start_out[k] = end_out[k] = 0;
+        atomicAdd(bad, 1);
+        return;
+    }
+    const int64_t e = s + 1;
+    start_out[k] = s;
+    end_out[k] = e;
+    pols[k] = events[(size_t)e * 4 + 3];
+    const float x = events[(size_t)s * 4], y = events[(size_t)s * 4 + 1];
+    if (!ray_pair(knots, rot, rotvec, tcoef, K, in, x, y, (double)events[(size_t)s * 4 + 2],
+                  (double)events[(size_t)e * 4 + 2], k, o1, d1, o2, d2))
+        atomicAdd(outside, 1);
+}
+
+// --negative_event_sampling (provider.py:1443-1476): pixel idx[k] of one chunk's event-free pixels, two uniform times of
+// the chunk in ascending order (microseconds; the track is in nanoseconds), rays through the camera at both.
+__global__ void __launch_bounds__(256) k_no_event_rays(
+    const float* __restrict__ coords, uint32_t n_coords, const int64_t* __restrict__ idx, const double* __restrict__ u,
+    uint32_t n, double t0, double t1, const double* __restrict__ knots, const double* __restrict__ rot,
+    const double* __restrict__ rotvec, const double* __restrict__ tcoef, uint32_t K, Intr in, float* __restrict__ o1,
+    float* __restrict__ d1, float* __restrict__ o2, float* __restrict__ d2, double* __restrict__ tss,
+    int* __restrict__ outside, int* __restrict__ bad) {
+    const uint32_t k = blockIdx.x * blockDim.x + threadIdx.x;
+    if (k >= n) return;
+    const int64_t i = idx[k];
+    if (i < 0 || i >= (int64_t)n_coords) {
+        zero_rays(k, o1, d1, o2, d2);
+        tss[(size_t)k * 2] = tss[(size_t)k * 2 + 1] = 0.0;
+        atomicAdd(bad, 1);
+        return;
+    }
+    const double span = t1 - t0;
+    const double ta = t0 + span * u[(size_t)k * 2], tb = t0 + span * u[(size_t)k * 2 + 1];
+    const double lo = ta < tb ? ta : tb, hi = ta < tb ? tb : ta;     // np.sort(..., axis=1)
+    tss[(size_t)k * 2] = lo;
+    tss[(size_t)k * 2 + 1] = hi;
+    if (!ray_pair(knots, rot, rotvec, tcoef, K, in, coords[(size_t)i * 2], coords[(size_t)i * 2 + 1], lo * 1000.0,
+                  hi * 1000.0, k, o1, d1, o2, d2))
+        atomicAdd(outside, 1);
 }
 
 
@@ -194,6 +228,46 @@ extern "C" int enerf_event_pair_rays(const float* events, const uint8_t* no_succ
         events, no_successor, num_successor, pol_cumsum, N, start_draw, u_end, M, acc_max_num_evs, knots, rot, rotvec,
         tcoef, K, in, rays_o1, rays_d1, rays_o2, rays_d2, pols, start_out, end_out, (int*)outside_track);
     ENERF_LAUNCH_CHECK("event_pair_rays");
+    return 0;
+}
+
+extern "C" int enerf_event_single_pair_rays(const float* events, uint32_t N, const int64_t* num_at_xy,
+                                            const int64_t* first_at_xy, uint32_t P, const double* u_xy,
+                                            const int64_t* choice, uint32_t M, const double* knots, const double* rot,
+                                            const double* rotvec, const double* tcoef, uint32_t K, float fx, float fy,
+                                            float cx, float cy, float* rays_o1, float* rays_d1, float* rays_o2,
+                                            float* rays_d2, float* pols, int64_t* start_out, int64_t* end_out,
+                                            int32_t* outside_track, int32_t* bad_choice, enerf_stream_t stream) {
+    if (M == 0) return 0;
+    if (N < 2 || P < 1 || K < 2)
+        ENERF_BADARG("event_single_pair_rays: need >= 2 events, >= 1 pixel and >= 2 track poses (N=%u P=%u K=%u)", N, P, K);
+    if (!events || !num_at_xy || !first_at_xy || !u_xy || !choice || !knots || !rot || !rotvec || !tcoef || !rays_o1 ||
+        !rays_d1 || !rays_o2 || !rays_d2 || !pols || !start_out || !end_out || !outside_track || !bad_choice)
+        ENERF_BADARG("event_single_pair_rays: null pointer");
+    const Intr in = {fx, fy, cx, cy};
+    k_event_single_pair_rays<<<div_up(M, 256), 256, 0, (hipStream_t)stream>>>(
+        events, N, num_at_xy, first_at_xy, P, u_xy, choice, M, knots, rot, rotvec, tcoef, K, in, rays_o1, rays_d1, rays_o2,
+        rays_d2, pols, start_out, end_out, (int*)outside_track, (int*)bad_choice);
+    ENERF_LAUNCH_CHECK("event_single_pair_rays");
+    return 0;
+}
+
+extern "C" int enerf_no_event_rays(const float* coords, uint32_t n_coords, const int64_t* idx, const double* u, uint32_t n,
+                                   double t0_us, double t1_us, const double* knots, const double* rot,
+                                   const double* rotvec, const double* tcoef, uint32_t K, float fx, float fy, float cx,
+                                   float cy, float* rays_o1, float* rays_d1, float* rays_o2, float* rays_d2,
+                                   double* tss_out, int32_t* outside_track, int32_t* bad_index, enerf_stream_t stream) {
+    if (n == 0) return 0;
+    if (n_coords < 1 || K < 2) ENERF_BADARG("no_event_rays: need >= 1 pixel and >= 2 track poses (n_coords=%u K=%u)", n_coords, K);
+    if (!coords || !idx || !u || !knots || !rot || !rotvec || !tcoef || !rays_o1 || !rays_d1 || !rays_o2 || !rays_d2 ||
+        !tss_out || !outside_track || !bad_index)
+        ENERF_BADARG("no_event_rays: null pointer");
+    const Intr in = {fx, fy, cx, cy};
+    k_no_event_rays<<<div_up(n, 256), 256, 0, (hipStream_t)stream>>>(coords, n_coords, idx, u, n, t0_us, t1_us, knots, rot,
+                                                                     rotvec, tcoef, K, in, rays_o1, rays_d1, rays_o2,
+                                                                     rays_d2, tss_out, (int*)outside_track,
+                                                                     (int*)bad_index);
+    ENERF_LAUNCH_CHECK("no_event_rays");
     return 0;
 }
 

@@ -9,6 +9,11 @@ Here both are tensor programs that run where the tensors live (HIP device in pro
   build_event_tables   events (x, y, t, p) -> pixel-grouped list + successor tables + polarity prefix sums
   sample_event_pairs   one step's pairs: start / end indices, summed polarities, pixel coordinates
   event_pair_batch     ... + pose gather + get_event_rays = the `rays_evs_*` / `pols` entries of the data dict
+  event_pair_rays / event_single_pair_rays / no_event_pair_rays
+                       one launch each (csrc/event_pairs.hip), poses from the PoseTrack inside the kernel: accumulation
+                       windows, direct-successor pairs (`accumulate_evs = 0`, what the shipped configs train with), and
+                       the no-event rays of `--negative_event_sampling`
+  EventSampler         .batch(index) -> the data dict of TrainHarness.step_events
 
 Given the same random draws the results are those of the reference's loops (oracle/event_collate.py restates them;
 tests/test_event_sampler.py).  The draws themselves come from a torch generator instead of numpy's global state.
@@ -116,6 +121,18 @@ def event_pair_batch(tables, poses_evs, intrinsics, batch_size, accumulate=True,
     return rays
 
 
+def _packed(tables):
+    """The layout the kernels read, built once per event batch: fp32 events, u8 no_successor, i64 num_successor, f64
+    pol_cumsum (event_pair_rays), i64 num_at_xy, i64 first_at_xy (event_single_pair_rays), all contiguous."""
+    if "_packed" not in tables or len(tables["_packed"]) < 6:
+        tables["_packed"] = (tables["events"].float().contiguous(), tables["no_successor"].to(torch.uint8).contiguous(),
+                             tables["num_successor"].to(torch.int64).contiguous(),
+                             tables["pol_cumsum"].to(torch.float64).contiguous(),
+                             tables["num_at_xy"].to(torch.int64).contiguous(),
+                             tables["first_at_xy"].to(torch.int64).contiguous())
+    return tables["_packed"]
+
+
 def event_pair_rays(tables, track, intrinsics, batch_size, acc_max_num_evs=0, generator=None, draws=None):
     """One step's event entries of collate (provider.py:1364-1441, accumulate_evs, poses computed online) as ONE launch
     on the device: pair selection + polarity sums + pose interpolation at both event times (PoseTrack) + ray generation
@@ -130,11 +147,7 @@ def event_pair_rays(tables, track, intrinsics, batch_size, acc_max_num_evs=0, ge
     draws = draws or {}
     start = draws["start"].to(dev) if "start" in draws else torch.randint(0, N, (M,), device=dev, generator=generator)
     u = draws["u_end"].to(dev) if "u_end" in draws else torch.rand(M, device=dev, generator=generator, dtype=torch.float64)
-    if "_packed" not in tables:        # the layout the kernel reads, built once per event batch
-        tables["_packed"] = (ev.float().contiguous(), tables["no_successor"].to(torch.uint8).contiguous(),
-                             tables["num_successor"].to(torch.int64).contiguous(),
-                             tables["pol_cumsum"].to(torch.float64).contiguous())
-    evf, nos, nsucc, cs = tables["_packed"]
+    evf, nos, nsucc, cs = _packed(tables)[:4]
     f32 = dict(dtype=torch.float32, device=dev)
     o1, d1, o2, d2 = (torch.empty(M, 3, **f32) for _ in range(4))
     pols = torch.empty(M, **f32)
@@ -150,6 +163,53 @@ def event_pair_rays(tables, track, intrinsics, batch_size, acc_max_num_evs=0, ge
         L.stream_handle()), "event_pair_rays")
     return {"rays_evs_o1": o1[None], "rays_evs_d1": d1[None], "rays_evs_o2": o2[None], "rays_evs_d2": d2[None],
             "pols": pols[None], "start": s_out, "end": e_out, "outside_track": outside}
+
+
+def event_single_pair_rays(tables, track, intrinsics, batch_size, generator=None, draws=None):
+    """One step's event entries of collate with `accumulate_evs = 0` (provider.py:1400-1441, the branch every shipped
+    config takes; poses computed online) as ONE launch on the device: per chosen pixel the drawn event that has a
+    successor, its direct successor, the successor's polarity, pose interpolation at both event times (PoseTrack) and
+    the rays (csrc/event_pairs.hip: k_event_single_pair_rays).  The statement is sample_event_pairs(accumulate=False) +
+    PoseTrack.poses_at + get_event_rays; no per-event pose array is needed.
+    Draws: u_xy = rand(P) in float64, one per kept pixel; choice = randperm(P)[:M] when M <= P (distinct pixels), else
+    randint(0, P, M) -- np.random.choice's `replace = batch_size > len(eidx)`.  `draws` = {"u_xy", "choice"} replaces them.
+    -> the dict of event_pair_rays + "bad_choice" (int32 [1]: entries of `choice` outside [0, P); their rows are zero)."""
+    from . import _lib as L
+    ev = tables["events"]
+    dev = ev.device
+    if not ev.is_cuda:
+        raise RuntimeError("event_single_pair_rays runs on the device; the host route is sample_event_pairs("
+                           "accumulate=False) + PoseTrack.poses_at + get_event_rays")
+    evf, _, _, _, num, first = _packed(tables)
+    N, P, M = evf.shape[0], num.shape[0], int(batch_size)
+    draws = draws or {}
+    u = draws["u_xy"].to(dev) if "u_xy" in draws else torch.rand(P, device=dev, generator=generator, dtype=torch.float64)
+    if "choice" in draws:
+        choice = draws["choice"].to(dev)
+    elif M > P:
+        choice = torch.randint(0, P, (M,), device=dev, generator=generator)
+    else:
+        choice = torch.randperm(P, device=dev, generator=generator)[:M]
+    u = u.to(torch.float64).contiguous()
+    choice = choice.to(torch.int64).contiguous()
+    if u.numel() != P or choice.numel() != M:
+        raise ValueError(f"event_single_pair_rays: u_xy has {u.numel()} entries for {P} pixels, choice {choice.numel()} "
+                         f"for {M} pairs")
+    f32 = dict(dtype=torch.float32, device=dev)
+    o1, d1, o2, d2 = (torch.empty(M, 3, **f32) for _ in range(4))
+    pols = torch.empty(M, **f32)
+    s_out = torch.empty(M, dtype=torch.int64, device=dev)
+    e_out = torch.empty(M, dtype=torch.int64, device=dev)
+    counters = torch.zeros(2, dtype=torch.int32, device=dev)
+    outside, bad = counters[0:1], counters[1:2]
+    fx, fy, cx, cy = (float(v) for v in intrinsics)
+    L.check(L.lib().enerf_event_single_pair_rays(
+        evf.data_ptr(), N, num.data_ptr(), first.data_ptr(), P, u.data_ptr(), choice.data_ptr(), M,
+        track.knots.data_ptr(), track.rot.data_ptr(), track.rotvec.data_ptr(), track.tcoef.data_ptr(), track.K, fx, fy, cx,
+        cy, o1.data_ptr(), d1.data_ptr(), o2.data_ptr(), d2.data_ptr(), pols.data_ptr(), s_out.data_ptr(), e_out.data_ptr(),
+        outside.data_ptr(), bad.data_ptr(), L.stream_handle()), "event_single_pair_rays")
+    return {"rays_evs_o1": o1[None], "rays_evs_d1": d1[None], "rays_evs_o2": o2[None], "rays_evs_d2": d2[None],
+            "pols": pols[None], "start": s_out, "end": e_out, "outside_track": outside, "bad_choice": bad}
 
 
 # ------------------------------------------------------------------------------------------------ negative events
@@ -235,3 +295,174 @@ def no_event_rays(no_evs, track, intrinsics, batch_size_evs, generator=None, dra
     r = get_event_rays(xs, ys, p1.unsqueeze(0), p2.unsqueeze(0), intrinsics)
     return {"rays_no_evs_o1": r["rays_evs_o1"], "rays_no_evs_d1": r["rays_evs_d1"],
             "rays_no_evs_o2": r["rays_evs_o2"], "rays_no_evs_d2": r["rays_evs_d2"], "chunk": j, "tss_us": tss}
+
+
+def no_event_pair_rays(no_evs, track, intrinsics, batch_size_evs, generator=None, draws=None):
+    """no_event_rays as ONE launch on the device (csrc/event_pairs.hip: k_no_event_rays): the pixel gather, the two
+    ordered times, the camera at both (PoseTrack, in the kernel) and the rays.  Same draws and same result entries as
+    no_event_rays, which stays the statement.  The chunk is always drawn on the host (`generator` when it is a CPU
+    generator, torch's CPU stream otherwise), so nothing is read back; the pixel indices and the uniforms are drawn on
+    the device unless `generator` lives on the CPU.  `draws` = {"chunk", "idx" [n], "u" [n, 2]}.
+    -> the dict of no_event_rays + "outside_track", "bad_index" (int32 [1]; rows of a bad index are zero)."""
+    from . import _lib as L
+    draws = draws or {}
+    n = int(batch_size_evs * 0.5)
+    n_chunks = int(no_evs["N_ev_chunks"])
+    dev = no_evs["coords"][0].device
+    if dev.type != "cuda":
+        raise RuntimeError("no_event_pair_rays runs on the device; the host route is no_event_rays")
+    on_host = generator is not None and generator.device.type == "cpu"
+    if "chunk" in draws:
+        j = int(draws["chunk"])
+    else:
+        j = int(torch.randint(0, n_chunks, (1,), generator=generator if on_host else None))
+    coords = no_evs["coords"][j]
+    if coords.shape[0] == 0:
+        raise ValueError(f"no-event chunk {j} is empty")
+    if coords.dim() != 2 or coords.shape[1] != 2:
+        raise ValueError(f"no-event chunk {j}: coords {tuple(coords.shape)}, [n, 2] expected")
+    if coords.dtype != torch.float32 or not coords.is_contiguous():
+        coords = coords.float().contiguous()
+    gdev = "cpu" if on_host else dev
+    idx = draws["idx"] if "idx" in draws else torch.randint(0, coords.shape[0], (n,), device=gdev, generator=generator)
+    u = draws["u"] if "u" in draws else torch.rand(n, 2, device=gdev, generator=generator, dtype=torch.float64)
+    idx = idx.to(dev, torch.int64).contiguous()
+    u = u.to(dev, torch.float64).contiguous()
+    if idx.numel() != n or tuple(u.shape) != (n, 2):
+        raise ValueError(f"no_event_pair_rays: {n} pixels need idx [{n}] and u [{n}, 2], got {tuple(idx.shape)} and "
+                         f"{tuple(u.shape)}")
+    t0, t1 = float(no_evs["start_time_us"][j]), float(no_evs["end_time_us"][j])
+    f32 = dict(dtype=torch.float32, device=dev)
+    o1, d1, o2, d2 = (torch.empty(n, 3, **f32) for _ in range(4))
+    tss = torch.empty(n, 2, dtype=torch.float64, device=dev)
+    counters = torch.zeros(2, dtype=torch.int32, device=dev)
+    outside, bad = counters[0:1], counters[1:2]
+    fx, fy, cx, cy = (float(v) for v in intrinsics)
+    L.check(L.lib().enerf_no_event_rays(
+        coords.data_ptr(), coords.shape[0], idx.data_ptr(), u.data_ptr(), n, t0, t1, track.knots.data_ptr(),
+        track.rot.data_ptr(), track.rotvec.data_ptr(), track.tcoef.data_ptr(), track.K, fx, fy, cx, cy, o1.data_ptr(),
+        d1.data_ptr(), o2.data_ptr(), d2.data_ptr(), tss.data_ptr(), outside.data_ptr(), bad.data_ptr(),
+        L.stream_handle()), "no_event_rays")
+    return {"rays_no_evs_o1": o1[None], "rays_no_evs_d1": d1[None], "rays_no_evs_o2": o2[None], "rays_no_evs_d2": d2[None],
+            "chunk": j, "tss_us": tss, "outside_track": outside, "bad_index": bad}
+
+
+# ------------------------------------------------------------------------------------------------ the sampler
+class EventSampler:
+    """The event side of EventNeRFDataset.collate (provider.py:1364-1476) for TrainHarness.step_events: one event batch
+    per frame index, `batch_size_evs` event pairs per step and, with `no_events`, batch_size_evs / 2 no-event pixels.
+
+      event_batches    per frame index an [E, 4] event tensor (x, y, t_ns, polarity; grouped here, in fp32 as the
+                       reference holds them) or the result of build_event_tables
+      track            the PoseTrack of the sequence (nanoseconds), on the events' device
+      intrinsics_evs   (fx, fy, cx, cy) of the event camera
+      accumulate_evs   false (every shipped config): direct-successor pairs; true: accumulation windows of at most
+                       acc_max_num_evs + 1 events (0: unbounded)
+      no_events        per frame index the result of build_no_event_tables (`--negative_event_sampling`), or None
+      frames           a FrameSampler whose batch of the same index supplies rays_o / rays_d / images, or None
+      seed             seeds the sampler's two generators: one on the tables' device for every draw but the no-event
+                       chunk, which comes from the one on the CPU so that it never has to be read back
+      H, W             the data dict's "H" / "W" (default: the frame sampler's; absent without either)
+
+    On device tables .batch() is the draws plus one launch for the pairs and one for the no-event rays, and waits for
+    nothing on the device.  On CPU tables it runs the statements: sample_event_pairs + PoseTrack.poses_at + get_event_rays,
+    and no_event_rays."""
+
+    def __init__(self, event_batches, track, intrinsics_evs, batch_size_evs, accumulate_evs=0, acc_max_num_evs=0,
+                 no_events=None, frames=None, seed=None, H=None, W=None):
+        if torch.is_tensor(event_batches) or isinstance(event_batches, dict):
+            event_batches = [event_batches]
+        self.tables = [b if isinstance(b, dict) else build_event_tables(torch.as_tensor(b).float())
+                       for b in event_batches]
+        if not self.tables:
+            raise ValueError("EventSampler: no event batch")
+        self.device = self.tables[0]["events"].device
+        for v, tab in enumerate(self.tables):
+            if tab["events"].device != self.device:
+                raise ValueError(f"EventSampler: event batch {v} lives on {tab['events'].device}, batch 0 on {self.device}")
+            if tab["events"].shape[0] < 2 or tab["num_at_xy"].shape[0] < 1:
+                raise ValueError(f"EventSampler: event batch {v} has no pixel with two events")
+        if track.knots.device != self.device:
+            raise ValueError(f"EventSampler: the track lives on {track.knots.device}, the events on {self.device}")
+        if no_events is not None:
+            if isinstance(no_events, dict):
+                no_events = [no_events]
+            if len(no_events) != len(self.tables):
+                raise ValueError(f"EventSampler: {len(no_events)} no-event tables for {len(self.tables)} event batches")
+        self.no_events = no_events
+        self.track = track
+        self.intrinsics = tuple(float(a) for a in intrinsics_evs)
+        self.batch_size_evs = int(batch_size_evs)
+        self.accumulate_evs = bool(accumulate_evs)
+        self.acc_max_num_evs = int(acc_max_num_evs)
+        self.frames = frames
+        self.H = H if H is not None else getattr(frames, "H", None)
+        self.W = W if W is not None else getattr(frames, "W", None)
+        self.generator = torch.Generator(device=self.device)
+        self.host_generator = torch.Generator()
+        if seed is None:
+            self.generator.seed()
+            self.host_generator.seed()
+        else:
+            self.generator.manual_seed(int(seed))
+            self.host_generator.manual_seed(int(seed))
+
+    def _view(self, index):
+        if torch.is_tensor(index):
+            index = index.reshape(-1).tolist()
+        elif not isinstance(index, (list, tuple)):
+            index = [index]
+        if len(index) != 1:
+            raise ValueError(f"one event batch per step: index {list(index)}")
+        v = int(index[0])
+        if not 0 <= v < len(self.tables):
+            raise ValueError(f"event batch {v} of {len(self.tables)}")
+        return v
+
+    def _pairs_statement(self, tab, draws):
+        s, e, pols, xs, ys = sample_event_pairs(tab, self.batch_size_evs, self.accumulate_evs, self.acc_max_num_evs,
+                                                self.generator, draws)
+        t = tab["events"][:, 2]
+        rays = get_event_rays(xs, ys, self.track.poses_at(t[s]).unsqueeze(0), self.track.poses_at(t[e]).unsqueeze(0),
+                              self.intrinsics)
+        rays.update(pols=pols, start=s, end=e)
+        return rays
+
+    def batch(self, index, draws=None):
+        """-> the data dict of TrainHarness.step_events: "rays_evs_o1/d1/o2/d2" [1, M, 3], "pols" [1, M]; with
+        `no_events` "rays_no_evs_o1/d1/o2/d2" [1, M / 2, 3]; with `frames` that sampler's "rays_o", "rays_d", "images"
+        (and "inds", "inds_coarse"), without it an empty "images" [1, 0, 3]; "index", "H", "W"; and what the step does not
+        read: "start" / "end" [M] (the pairs' events), "chunk", "tss_us", and on the device the counters
+        "outside_track", "bad_choice", "no_evs_outside_track", "no_evs_bad_index" (int32 [1] each, never read here).
+        `draws` replaces random draws by name: {"u_xy", "choice"} or {"start", "u_end"} for the pairs, {"chunk", "idx",
+        "u"} for the no-event rays, and FrameSampler.batch's for the frames."""
+        v = self._view(index)
+        tab = self.tables[v]
+        cuda = self.device.type == "cuda"
+        draws = draws or {}
+        if not cuda:
+            out = self._pairs_statement(tab, draws)
+        elif self.accumulate_evs:
+            out = event_pair_rays(tab, self.track, self.intrinsics, self.batch_size_evs, self.acc_max_num_evs,
+                                  self.generator, draws)
+        else:
+            out = event_single_pair_rays(tab, self.track, self.intrinsics, self.batch_size_evs, self.generator, draws)
+        if self.no_events is not None:
+            no_evs = self.no_events[v]
+            if "chunk" not in draws:
+                draws = dict(draws, chunk=int(torch.randint(0, int(no_evs["N_ev_chunks"]), (1,),
+                                                            generator=self.host_generator)))
+            r = (no_event_pair_rays if cuda else no_event_rays)(no_evs, self.track, self.intrinsics, self.batch_size_evs,
+                                                                self.generator, draws)
+            for k in ("outside_track", "bad_index"):
+                if k in r:
+                    out["no_evs_" + k] = r.pop(k)
+            out.update(r)
+        if self.frames is not None:
+            out.update(self.frames.batch([v], generator=self.generator, draws=draws))
+        else:
+            out["images"] = torch.empty(1, 0, 3, dtype=torch.float32, device=self.device)
+        out["index"] = [v]
+        if self.H is not None and self.W is not None:
+            out["H"], out["W"] = int(self.H), int(self.W)
+        return out

@@ -60,8 +60,10 @@ const char* enerf_last_error(void);
  * 7: enerf_train_step_args gained next_count_host; `reserved` of both step structs became `report`, written by the library
  *    (the argument pointers lost their const); flags bit 2 of both = every row through the networks.
  * 8: enerf_frame_batch and enerf_error_map_* added (frame batches, the reference's --error_map).
- * 9: enerf_debug_nerf_bwd_transpose added (how the fused MLP backward transposes its weight-gradient operands). */
-#define ENERF_ABI_VERSION 9
+ * 9: enerf_debug_nerf_bwd_transpose added (how the fused MLP backward transposes its weight-gradient operands).
+ * 10: enerf_event_single_pair_rays and enerf_no_event_rays added (the event side of collate with accumulate_evs off, and
+ *     the rays of --negative_event_sampling). */
+#define ENERF_ABI_VERSION 10
 int enerf_abi_version(void);
 /* The library keeps grow-only scratch buffers per device (march chunk log, grid-backward record lists, ...).  Growing one
  * frees the old allocation; the counter returned here moves every time that happens.  A caller that captured library
@@ -613,6 +615,30 @@ int enerf_event_pair_rays(const float* events, const uint8_t* no_successor, cons
                           const double* rotvec, const double* tcoef, uint32_t K, float fx, float fy, float cx, float cy,
                           float* rays_o1, float* rays_d1, float* rays_o2, float* rays_d2, float* pols,
                           int64_t* start_out, int64_t* end_out, int32_t* outside_track, enerf_stream_t stream);
+
+/* The same with accumulate_evs off (nerf/provider.py:1400-1405, the branch every shipped config takes), one thread per
+ * pair: c = choice[k]; s = (int64) trunc(u_xy[c] * (double) num_at_xy[c] - 1.0) + first_at_xy[c] (the product and the
+ * difference each rounded; truncation toward zero: (np.random.rand(P) * num - 1).astype(int) + first); e = s + 1;
+ * pols[k] = events[e].polarity; pixel of event s, poses at events[s].t and events[e].t, rays as above.
+ * num_at_xy / first_at_xy i64 [P] (events per kept pixel, index of its first event); u_xy f64 [P] in [0,1); choice i64 [M].
+ * A choice[k] outside [0, P) -- or an s outside [0, N - 2], which no valid table and u_xy > 0 produce -- reads nothing:
+ * the pair's outputs are zero and *bad_choice += 1.  *outside_track as above.  M == 0: no launch. */
+int enerf_event_single_pair_rays(const float* events, uint32_t N, const int64_t* num_at_xy, const int64_t* first_at_xy,
+                                 uint32_t P, const double* u_xy, const int64_t* choice, uint32_t M, const double* knots,
+                                 const double* rot, const double* rotvec, const double* tcoef, uint32_t K, float fx,
+                                 float fy, float cx, float cy, float* rays_o1, float* rays_d1, float* rays_o2,
+                                 float* rays_d2, float* pols, int64_t* start_out, int64_t* end_out,
+                                 int32_t* outside_track, int32_t* bad_choice, enerf_stream_t stream);
+/* The no-event rays of --negative_event_sampling (nerf/provider.py:1443-1476), one thread per pixel: pixel
+ * coords[idx[k]] (x, y) of one chunk's event-free pixels; ta = t0_us + (t1_us - t0_us) * u[k][0], tb likewise (each
+ * operation rounded), tss_out[k] = (min, max) in microseconds; poses at 1000 * those (the track is in nanoseconds), rays as
+ * above.  coords fp32 [n_coords,2]; idx i64 [n]; u f64 [n,2]; tss_out f64 [n,2].  An idx[k] outside [0, n_coords) reads
+ * nothing: zero outputs, *bad_index += 1.  *outside_track += pixels with a time outside the track.  n == 0: no launch. */
+int enerf_no_event_rays(const float* coords, uint32_t n_coords, const int64_t* idx, const double* u, uint32_t n,
+                        double t0_us, double t1_us, const double* knots, const double* rot, const double* rotvec,
+                        const double* tcoef, uint32_t K, float fx, float fy, float cx, float cy, float* rays_o1,
+                        float* rays_d1, float* rays_o2, float* rays_d2, double* tss_out, int32_t* outside_track,
+                        int32_t* bad_index, enerf_stream_t stream);
 
 /* The event loss of Trainer.train_step_events (nerf/utils.py:499-516, C_thres != -1) and its gradient with respect to
  * the two rendered images, one launch: image1 / image2 [N,3] fp32, pols [N] -> delta [N,1] (use_luma) or [N,3],
