@@ -118,6 +118,7 @@ SIGNATURES = {
     "enerf_prof_reset": [],
     "enerf_prof_read": [_int, _c.POINTER(_c.c_double), _c.POINTER(_c.c_uint64)],
     "enerf_adam_step_multi": [_u32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _f32, _f32, _f32, _int, _vp],
+    "enerf_ema_update_multi": [_u32, _vp, _vp, _vp, _f32, _vp],
     "enerf_prof_enable_mask": [_u32],
     "enerf_prof_sample_every": [_u32],
     "enerf_prof_read_units": [_int, _c.POINTER(_c.c_double), _c.POINTER(_c.c_uint64)],

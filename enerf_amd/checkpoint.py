@@ -2,7 +2,7 @@
 reads (nerf/utils.py:1295-1351, 1353-1415):
 
     {'epoch', 'global_step', 'stats', ['mean_count', 'mean_density' when cuda_ray],
-     ['optimizer', 'lr_scheduler', 'scaler' when full], 'model': state_dict}
+     ['optimizer', 'lr_scheduler', 'scaler', and 'ema' when the run keeps an average, when full], 'model': state_dict}
 
 so that a run trained by the reference resumes on this path and the other way round.  The model's module / parameter /
 buffer names are the reference's (tests/golden/ref_state_dict_schema.json); what needs care is the optimizer:
@@ -66,12 +66,40 @@ def checkpoint_dict(harness, full=False):
             state["lr_scheduler"] = sched.state_dict()
         scaler = getattr(harness, "scaler", None)
         state["scaler"] = scaler.state_dict() if scaler is not None else {}
+        ema = getattr(harness, "ema", None)
+        if ema is not None:
+            state["ema"] = ema.state_dict()   # (nerf/utils.py:1314-1315; enerf_amd/ema.py: torch_ema's format)
     state["model"] = m.state_dict()
     return state
 
 
-def save_checkpoint(harness, path, full=False):
-    torch.save(checkpoint_dict(harness, full=full), path)
+def save_checkpoint(harness, path, full=False, best=False):
+    """`best` (nerf/utils.py:1333-1351): only when the last evaluated result beats stats['best_result'], and then with
+    the average's weights under 'model' when the harness keeps one (store, copy_to, state_dict, restore).  -> path, or
+    None when nothing was written."""
+    if not best:
+        torch.save(checkpoint_dict(harness, full=full), path)
+        return path
+    stats = harness.stats
+    if len(stats["results"]) == 0:
+        import warnings
+        warnings.warn("[checkpoint] no evaluated results found, skip saving best checkpoint.")
+        return None
+    if stats["best_result"] is not None and not stats["results"][-1] < stats["best_result"]:
+        return None
+    stats["best_result"] = stats["results"][-1]
+    ema = getattr(harness, "ema", None)
+    if ema is not None:
+        ema.store()
+        ema.copy_to()
+    try:
+        state = checkpoint_dict(harness, full=full)
+        if ema is not None:         # (state_dict() hands out the parameters themselves, which restore() overwrites)
+            state["model"] = {k: v.detach().clone() for k, v in state["model"].items()}
+    finally:
+        if ema is not None:
+            ema.restore()
+    torch.save(state, path)
     return path
 
 
@@ -145,6 +173,9 @@ def load_checkpoint(harness, checkpoint, model_only=False, map_location=None, tr
         epoch = getattr(raymarching, "BITFIELD_EPOCH", None)
         if epoch is not None:
             epoch[0] += 1
+    ema = getattr(harness, "ema", None)
+    if ema is not None and "ema" in checkpoint:       # (before the model_only return, as nerf/utils.py:1379-1380)
+        ema.load_state_dict(checkpoint["ema"])
     if model_only:
         return list(missing), list(unexpected)
     if "stats" in checkpoint:

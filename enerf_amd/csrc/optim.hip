@@ -97,6 +97,52 @@ __global__ void __launch_bounds__(256) k_adam_multi(AdamTable tab, float b1, flo
     }
 }
 
+// The parameters' exponential moving average (enerf_amd/ema.py ParamEMA.update; torch_ema's `tmp = s - p; tmp.mul_(omd);
+// s.sub_(tmp)`): read s and p, write s -- 12 B/element, one launch for all tensors with k_adam_multi's block -> tensor map.
+// Three fp32 operations, each rounded once (the library is built with -ffp-contract=off); NaN and inf take no special path.
+struct EmaTable {
+    float* s[kMaxAdamTensors];
+    const float* p[kMaxAdamTensors];
+    unsigned long long n[kMaxAdamTensors];
+    uint32_t first_block[kMaxAdamTensors + 1];
+    uint32_t count;
+    uint32_t vec_mask;      // bit t: both pointers of tensor t are 16-byte aligned (float4 body + scalar tail)
+};
+
+__device__ __forceinline__ float ema1(float s, float p, float omd) {
+    const float d = s - p;
+    const float t = d * omd;
+    return s - t;
+}
+
+__global__ void __launch_bounds__(256) k_ema_multi(EmaTable tab, float omd) {
+    uint32_t t = 0;
+    while (t + 1 < tab.count && blockIdx.x >= tab.first_block[t + 1]) t++;
+    float* __restrict__ s = tab.s[t];
+    const float* __restrict__ p = tab.p[t];
+    const size_t n = tab.n[t];
+    const uint32_t nblk = tab.first_block[t + 1] - tab.first_block[t];
+    const uint32_t blk = blockIdx.x - tab.first_block[t];
+    const size_t stride = (size_t)nblk * blockDim.x;
+    const size_t first = (size_t)blk * blockDim.x + threadIdx.x;
+    if (!((tab.vec_mask >> t) & 1u)) {      // (wave-uniform: a property of the tensor)
+        for (size_t i = first; i < n; i += stride) s[i] = ema1(s[i], p[i], omd);
+        return;
+    }
+    const size_t n4 = n / 4;
+    for (size_t i = first; i < n4; i += stride) {
+        float4 S = reinterpret_cast<float4*>(s)[i];
+        const float4 P = reinterpret_cast<const float4*>(p)[i];
+        S.x = ema1(S.x, P.x, omd);
+        S.y = ema1(S.y, P.y, omd);
+        S.z = ema1(S.z, P.z, omd);
+        S.w = ema1(S.w, P.w, omd);
+        reinterpret_cast<float4*>(s)[i] = S;
+    }
+    const size_t tl = n4 * 4 + first;       // tail: fewer than 4 elements, the tensor's first block
+    if (tl < n) s[tl] = ema1(s[tl], p[tl], omd);
+}
+
 // torch.amp.GradScaler.update() (torch._amp_update_scale_) + the bookkeeping of a skipped step, one thread
 __global__ void k_amp_update(float* scale, int32_t* growth_tracker, uint32_t* found_inf, uint32_t* skipped,
                              float growth_factor, float backoff_factor, int32_t growth_interval) {
@@ -192,6 +238,42 @@ int enerf_adam_step_multi(uint32_t count, float* const* p, float* const* g, floa
     tab.count = count;
     k_adam_multi<<<blocks, 256, 0, (hipStream_t)stream>>>(tab, beta1, beta2, eps, zero_grad);
     ENERF_LAUNCH_CHECK("adam_step_multi");
+    return 0;
+}
+
+
+// shadow = shadow - (shadow - p) * one_minus_decay for up to 16 contiguous fp32 tensors in one launch: arrays of `count`
+// device pointers / sizes (host memory).  A tensor whose two pointers are 16-byte aligned is walked in 16-byte accesses
+// with a scalar tail, any other element by element; n[i] == 0 is a no-op.
+int enerf_ema_update_multi(uint32_t count, float* const* shadow, const float* const* p, const size_t* n,
+                           float one_minus_decay, enerf_stream_t stream) {
+    if (count == 0) return 0;
+    if (count > (uint32_t)kMaxAdamTensors) ENERF_BADARG("ema_update_multi: at most %d tensors per call, got %u", kMaxAdamTensors, count);
+    if (!shadow || !p || !n) ENERF_BADARG("ema_update_multi: the three host arrays are required");
+    EmaTable tab;
+    uint32_t blocks = 0;
+    tab.vec_mask = 0;
+    for (uint32_t t = 0; t < count; t++) {
+        if (n[t] > 0 && (!shadow[t] || !p[t])) ENERF_BADARG("ema_update_multi: tensor %u: null pointer with n = %zu", t, n[t]);
+        tab.s[t] = shadow[t]; tab.p[t] = p[t];
+        tab.n[t] = n[t];
+        const bool vec = (((uintptr_t)shadow[t] | (uintptr_t)p[t]) & 15) == 0;
+        if (vec) tab.vec_mask |= 1u << t;
+        uint32_t b = 0;
+        if (n[t] > 0) {
+            const size_t units = vec ? (n[t] / 4 ? n[t] / 4 : 1) : n[t];
+            const size_t want = (units + 255) / 256;
+            b = want > 2048u ? 2048u : (uint32_t)want;
+        }
+        tab.first_block[t] = blocks;
+        blocks += b;
+    }
+    for (uint32_t t = count; t <= (uint32_t)kMaxAdamTensors; t++) tab.first_block[t] = blocks;
+    for (uint32_t t = count; t < (uint32_t)kMaxAdamTensors; t++) { tab.s[t] = nullptr; tab.p[t] = nullptr; tab.n[t] = 0; }
+    tab.count = count;
+    if (blocks == 0) return 0;
+    k_ema_multi<<<blocks, 256, 0, (hipStream_t)stream>>>(tab, one_minus_decay);
+    ENERF_LAUNCH_CHECK("ema_update_multi");
     return 0;
 }
 

@@ -407,6 +407,10 @@ class EventSampler:
             self.generator.manual_seed(int(seed))
             self.host_generator.manual_seed(int(seed))
 
+    def __len__(self):
+        """The number of event batches: one step each per epoch (TrainHarness.train_one_epoch)."""
+        return len(self.tables)
+
     def _view(self, index):
         if torch.is_tensor(index):
             index = index.reshape(-1).tolist()

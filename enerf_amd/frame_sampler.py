@@ -182,6 +182,10 @@ class FrameSampler:
         self.error_map = (torch.ones(poses.shape[0], CELLS, dtype=torch.float32, device=poses.device)
                           if error_map else None)
 
+    def __len__(self):
+        """The number of views: one batch each per epoch (TrainHarness.train_one_epoch)."""
+        return int(self.poses.shape[0])
+
     def _view(self, index):
         if torch.is_tensor(index):
             index = index.reshape(-1).tolist()

@@ -26,8 +26,14 @@ _UNSET = object()
 
 class TrainHarness:
     def __init__(self, model, lr=1e-2, occupancy="synthetic", world=1, update_interval=16, use_graphs=False,
-                 optimizer=None, fp16=False, amp=None, prime_pool=None):
+                 optimizer=None, fp16=False, amp=None, prime_pool=None, ema_decay=None):
         self.model = model
+        # the parameters' exponential moving average (nerf/utils.py:370-373; main_nerf.py:214 trains with 0.95): what
+        # evaluate() renders with, what the "best" checkpoint holds, 'ema' in a full checkpoint; moved by train_one_epoch
+        self.ema = None
+        if ema_decay is not None:
+            from .ema import ParamEMA
+            self.ema = ParamEMA(model.parameters(), ema_decay)
         adam = optimizer or (FusedAdam if next(model.parameters()).is_cuda else torch.optim.Adam)
         self.opt = adam(model.get_params(lr), betas=(0.9, 0.99), eps=1e-15)
         self.occupancy = occupancy
@@ -225,10 +231,13 @@ class TrainHarness:
         self.opt._opt_called = True       # the harness calls step_now / step_grid_table, not the wrapped step()
         return self.lr_scheduler
 
-    def save_checkpoint(self, path, full=False):
-        """The reference's checkpoint dict (nerf/utils.py:1295-1351) -> `path`."""
+    def save_checkpoint(self, path, full=False, best=False):
+        """The reference's checkpoint dict (nerf/utils.py:1295-1351) -> `path`; a full one carries 'ema' when the harness
+        keeps an average.  `best` (:1333-1351): written only when stats["results"][-1] is below stats["best_result"] (or
+        there is none yet), which it then becomes, with the AVERAGE's weights under 'model' when there is one; -> None
+        when nothing was written (a warning when nothing has been evaluated yet)."""
         from .checkpoint import save_checkpoint
-        return save_checkpoint(self, path, full=full)
+        return save_checkpoint(self, path, full=full, best=best)
 
     def save_mesh(self, save_path, resolution=256, threshold=10):
         """The reference's Trainer.save_mesh (nerf/utils.py:712-732): sigma on a resolution^3 lattice over aabb_infer,
@@ -241,10 +250,77 @@ class TrainHarness:
         """The reference's Trainer.evaluate / evaluate_one_epoch (nerf/utils.py:763-766, 1028-1293) over `views` (the
         val split's collate dicts): the renders of eval_step / eval_step_tumvie under model.eval() in this harness's
         regime, PSNR and SSIM, or for `opt.event_only` the log-affine correction and its metrics; `ema` (store / copy_to /
-        restore) brackets the renders as there; rank 0 writes the validation/ tree under `save_dir`.  -> dict of floats
-        and lists (enerf_amd/evaluate.py)."""
+        restore; None: the harness's own average, if it keeps one) brackets the renders as there; rank 0 writes the
+        validation/ tree under `save_dir`.  -> dict of floats and lists (enerf_amd/evaluate.py)."""
         from .evaluate import harness_evaluate
-        return harness_evaluate(self, views, opt, name=name, save_dir=save_dir, ema=ema)
+        return harness_evaluate(self, views, opt, name=name, save_dir=save_dir, ema=self.ema if ema is None else ema)
+
+    def train_one_epoch(self, sampler, opt, order=None):
+        """The reference's Trainer.train_one_epoch (nerf/utils.py:920-1015) without its logging: one step per batch of
+        `sampler` (a FrameSampler or an EventSampler) in `order` (default: torch.randperm(len(sampler)) from torch's
+        global CPU generator, the DataLoader(shuffle=True) of the reference) -- step_events for a batch with
+        "rays_evs_o1", step_frames otherwise; the next batch is drawn before the current step is taken, so that the event
+        route can march it underneath.  The losses are summed on the device in fp64, in step order (the reference's
+        Python-float sum of fp32 losses), and read back once.  After the last step the average, if there is one, is
+        updated; -> the epoch's mean loss, also appended to stats["loss"].  `self.epoch` is train()'s to move."""
+        if order is None:
+            order = torch.randperm(len(sampler))
+        order = [int(i) for i in (order.tolist() if torch.is_tensor(order) else order)]
+        if not order:
+            raise ValueError("train_one_epoch: an empty epoch")
+        total = None
+        data = sampler.batch([order[0]])
+        for k in range(len(order)):
+            nxt = sampler.batch([order[k + 1]]) if k + 1 < len(order) else None
+            if "rays_evs_o1" in data:
+                loss = self.step_events(data, opt, nxt if nxt is not None and "rays_evs_o1" in nxt else None)
+            else:
+                loss = self.step_frames(data, opt, sampler)
+            loss = loss.detach().double()
+            total = loss.clone() if total is None else total.add_(loss)
+            data = nxt
+        if self.ema is not None:
+            self.ema.update()
+        mean = float(total) / len(order)
+        self.stats["loss"].append(mean)
+        return mean
+
+    def train(self, sampler, opt, max_epochs, valid_views=None, eval_interval=10, workspace=None, name="ngp",
+              max_keep_ckpt=2):
+        """The reference's Trainer.train (nerf/utils.py:734-761): for every epoch from `self.epoch` to `max_epochs`,
+        train_one_epoch; with a `workspace`, on rank 0, a full checkpoint {workspace}/checkpoints/{name}_ep{epoch:04d}.pth,
+        recorded in stats["checkpoints"], the oldest beyond `max_keep_ckpt` deleted (:1323-1329); every `eval_interval`
+        epochs, with `valid_views`, evaluate() -- its valid_loss appended to stats["valid_loss"] and stats["results"] (the
+        reference's default use_loss_as_metric=True) -- and the "best" checkpoint {workspace}/checkpoints/{name}.pth.
+        Marking the cells no training camera sees (model.mark_untrained_grid, which the reference calls here) stays the
+        caller's job, as for every other entry point of the harness.  -> stats."""
+        import os
+        import torch.distributed as dist
+        rank0 = not (dist.is_available() and dist.is_initialized()) or dist.get_rank() == 0
+        ckpt_dir = None
+        if workspace is not None:
+            ckpt_dir = os.path.join(workspace, "checkpoints")
+            if rank0:
+                os.makedirs(ckpt_dir, exist_ok=True)
+        for epoch in range(self.epoch, max_epochs + 1):
+            self.epoch = epoch
+            self.train_one_epoch(sampler, opt)
+            if ckpt_dir is not None and rank0:
+                path = os.path.join(ckpt_dir, f"{name}_ep{epoch:04d}.pth")
+                kept = self.stats["checkpoints"]
+                kept.append(path)
+                if len(kept) > max_keep_ckpt:
+                    old = kept.pop(0)
+                    if os.path.exists(old):
+                        os.remove(old)
+                self.save_checkpoint(path, full=True)
+            if valid_views is not None and epoch % eval_interval == 0:
+                r = self.evaluate(valid_views, opt, name=f"{name}_ep{epoch:04d}")
+                self.stats["valid_loss"].append(r["valid_loss"])
+                self.stats["results"].append(r["valid_loss"])
+                if ckpt_dir is not None and rank0:
+                    self.save_checkpoint(os.path.join(ckpt_dir, f"{name}.pth"), best=True)
+        return self.stats
 
     def load_checkpoint(self, checkpoint, model_only=False):
         """Resume from a checkpoint in the reference's format (nerf/utils.py:1353-1415), whoever wrote it."""

@@ -62,8 +62,9 @@ const char* enerf_last_error(void);
  * 8: enerf_frame_batch and enerf_error_map_* added (frame batches, the reference's --error_map).
  * 9: enerf_debug_nerf_bwd_transpose added (how the fused MLP backward transposes its weight-gradient operands).
  * 10: enerf_event_single_pair_rays and enerf_no_event_rays added (the event side of collate with accumulate_evs off, and
- *     the rays of --negative_event_sampling). */
-#define ENERF_ABI_VERSION 10
+ *     the rays of --negative_event_sampling).
+ * 11: enerf_ema_update_multi added (the parameters' exponential moving average, Trainer's ema_decay). */
+#define ENERF_ABI_VERSION 11
 int enerf_abi_version(void);
 /* The library keeps grow-only scratch buffers per device (march chunk log, grid-backward record lists, ...).  Growing one
  * frees the old allocation; the counter returned here moves every time that happens.  A caller that captured library
@@ -659,6 +660,14 @@ int enerf_adam_step(float* p, float* g, float* m, float* v, size_t n, float lr, 
 int enerf_adam_step_multi(uint32_t count, float* const* p, float* const* g, float* const* m, float* const* v,
                           const size_t* n, const float* lr, const uint32_t* step, float beta1, float beta2, float eps,
                           int zero_grad, enerf_stream_t stream);
+/* The exponential moving average of the parameters (torch_ema's update as nerf/utils.py:1005-1006 calls it; semantics in
+ * enerf_amd/ema.py and DESIGN.md 4.14): shadow[i] = shadow[i] - ((shadow[i] - p[i]) * one_minus_decay) element by element,
+ * three fp32 operations each rounded once, for up to 16 contiguous fp32 tensors in one launch.  Arrays of `count` device
+ * pointers / sizes (host memory).  A tensor whose two pointers are 16-byte aligned is walked in 16-byte accesses with a
+ * scalar tail, any other one element by element.  n[i] == 0 is a no-op (its pointers are not looked at); count == 0
+ * returns 0; count > 16, or a null pointer with n[i] > 0, is ENERF_E_BADARG. */
+int enerf_ema_update_multi(uint32_t count, float* const* shadow, const float* const* p, const size_t* n,
+                           float one_minus_decay, enerf_stream_t stream);
 
 /* ------------------------------------------------------------------ one training step as one call (not in the reference)
  * The closed-form RGB step of the nn.Linear / FFMLP networks on one GPU -- render of a batch whose samples have been
