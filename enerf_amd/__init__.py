@@ -13,8 +13,9 @@ There is no CPU fallback in this package: every hot-path call goes to libenerf_h
 """
 __version__ = "0.1.0"
 
-# the two data-side entry points, resolved on first use (importing the package stays free of torch)
-_EXPORTS = {"FrameSampler": "frame_sampler", "EventSampler": "event_sampler"}
+# the data-side entry points and the view renderer, resolved on first use (importing the package stays free of torch)
+_EXPORTS = {"FrameSampler": "frame_sampler", "EventSampler": "event_sampler", "ViewRenderer": "view",
+            "interpolate_poses": "render_path", "spiral_poses": "render_path", "poses_from_quat_list": "render_path"}
 __all__ = sorted(_EXPORTS)
 
 

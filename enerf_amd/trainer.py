@@ -255,6 +255,26 @@ class TrainHarness:
         from .evaluate import harness_evaluate
         return harness_evaluate(self, views, opt, name=name, save_dir=save_dir, ema=self.ema if ema is None else ema)
 
+    def test(self, views, opt, save_path, name=None, write_depth=None, write_behind=True):
+        """The reference's Trainer.test (nerf/utils.py:768-804) over `views` (dicts with rays_o, rays_d, H, W: a
+        FrameSampler(num_rays=-1) batch; images are not needed): test_step per view (bg_color None, perturb off, staged)
+        under model.eval() in this harness's regime, WITHOUT the average, as there; one enerf_view_finish launch makes the
+        bytes (linear_to_srgb for color_space = "linear") and `{save_path}/{name}_{i:04d}.png` -- grey for C = 1, RGB for
+        C = 3 -- is written behind the next view's render, `depth/{name}_{i:04d}_depth.png` with `write_depth` (default:
+        the reference's epoch % 100 == 0).  `name` defaults to ngp_ep{epoch:04d}.  Returns once every file is written
+        (`write_behind=False`: view by view, synchronously) -> the list of image paths (enerf_amd/view.py)."""
+        from .view import harness_test
+        return harness_test(self, views, opt, save_path, name=name, write_depth=write_depth, write_behind=write_behind)
+
+    def render_path(self, poses, intrinsics, H, W, opt, outdir, normalize=False, write_behind=True):
+        """The path loop of the reference's scripts/render.py:489-509 over cam2world `poses` [n, 3 or 4, 4] (see
+        enerf_amd/render_path.py): full-frame rays on the device, render with bg_color 1, `rgb/{i}.png`,
+        `depth/{i}_depth.png`, `raws/{i}.npy` under `outdir`; `normalize` is that script's per-frame min-max scaling
+        (enerf_view_minmax into enerf_view_finish; the raw frame is then the scaled one, as there).  -> the rgb paths."""
+        from .view import harness_render_path
+        return harness_render_path(self, poses, intrinsics, H, W, opt, outdir, normalize=normalize,
+                                   write_behind=write_behind)
+
     def train_one_epoch(self, sampler, opt, order=None):
         """The reference's Trainer.train_one_epoch (nerf/utils.py:920-1015) without its logging: one step per batch of
         `sampler` (a FrameSampler or an EventSampler) in `order` (default: torch.randperm(len(sampler)) from torch's

@@ -63,8 +63,10 @@ const char* enerf_last_error(void);
  * 9: enerf_debug_nerf_bwd_transpose added (how the fused MLP backward transposes its weight-gradient operands).
  * 10: enerf_event_single_pair_rays and enerf_no_event_rays added (the event side of collate with accumulate_evs off, and
  *     the rays of --negative_event_sampling).
- * 11: enerf_ema_update_multi added (the parameters' exponential moving average, Trainer's ema_decay). */
-#define ENERF_ABI_VERSION 11
+ * 11: enerf_ema_update_multi added (the parameters' exponential moving average, Trainer's ema_decay).
+ * 12: enerf_view_finish and enerf_view_minmax added (a rendered frame to display bytes: Trainer.test / test_gui, the GUI's
+ *     running mean, scripts/render.py's min-max scaling). */
+#define ENERF_ABI_VERSION 12
 int enerf_abi_version(void);
 /* The library keeps grow-only scratch buffers per device (march chunk log, grid-backward record lists, ...).  Growing one
  * frees the old allocation; the counter returned here moves every time that happens.  A caller that captured library
@@ -1023,6 +1025,34 @@ int enerf_error_map_update(float* map, const int64_t* inds_coarse, const float* 
  * a GPU hold the network to the statement with it). */
 int enerf_debug_error_map_sample_host(const float* weights, const float* e, const float* u_row, const float* u_col,
                                       uint32_t N, uint32_t H, uint32_t W, int64_t* inds_coarse, int64_t* inds);
+
+/* ------------------------------------------------------------------ display frames
+ * What the reference does on the host between a rendered fp32 frame and what is shown or written (nerf/utils.py:768-804
+ * Trainer.test, :870-918 test_gui, nerf/gui.py:119-149, scripts/render.py:489-509), csrc/view_finish.hip; semantics in
+ * enerf_amd/view.py and DESIGN.md 4.15.  Every fp32 operation below is rounded on its own (-ffp-contract=off).
+ *
+ * view_finish: ONE launch, one thread per output pixel, no intermediate in memory.  image fp32 [h*w, C] (C in 1..3), depth
+ *   fp32 [h*w] or NULL; the output is H x W.  Per output pixel (y, x) and channel:
+ *     1. source pixel: row = min((int)floorf(y * s_h), h - 1) with s_h = (float)h / (float)H, the column likewise: the
+ *        index of F.interpolate(mode="nearest", size=(H, W)) (the identity when (h, w) == (H, W));
+ *     2. minmax != NULL (device, fp32 [2] = min, max): v = max == min ? 0 : (v - min) / (max - min);
+ *     3. flags & ENERF_VIEW_LINEAR: v = v < 0.0031308 ? 12.92 v : 1.055 powf(v, 0.41666) - 0.055   (linear_to_srgb);
+ *     4. accum != NULL (fp32 [H*W, C], read and written): a = spp == 0 ? v : (a (float)spp + v) / (float)(spp + 1),
+ *        stored back, and v = a from here on (the GUI's running mean in numpy fp32); out_f32 may be accum itself (the
+ *        running buffer is then the fp32 result and is written once);
+ *     5. out_f32 [H*W, C] = v; out_u8 [H*W, C] = (uint8) of v * 255 clamped to [0, 255], truncated; NaN gives 0.
+ *   depth_f32 [H*W] / depth_u8 [H*W] take steps 1 and 5 only.  Every output pointer may be NULL.  Bad arguments: C outside
+ *   1..3; H*W == 0 together with a non-NULL output; accum with neither out_f32 nor out_u8; a depth output without depth;
+ *   an image of 0 or more than 2^30 pixels.
+ * view_minmax: minmax [2] (device) = the smallest and largest of the n image values, NaNs skipped; (0, 1) when there is
+ *   none.  Two launches (per-workgroup partials in ws, fp32 [ENERF_VIEW_MINMAX_WS] on the device, then one workgroup over
+ *   them), nothing is read back. */
+#define ENERF_VIEW_LINEAR 1u
+#define ENERF_VIEW_MINMAX_WS 512
+int enerf_view_finish(const float* image, const float* depth, uint32_t h, uint32_t w, uint32_t C, uint32_t H, uint32_t W,
+                      uint32_t flags, const float* minmax, float* accum, uint32_t spp, float* out_f32, uint8_t* out_u8,
+                      float* depth_f32, uint8_t* depth_u8, enerf_stream_t stream);
+int enerf_view_minmax(const float* image, uint64_t n, float* ws, float* minmax, enerf_stream_t stream);
 
 #ifdef __cplusplus
 }
