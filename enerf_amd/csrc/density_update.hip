@@ -326,6 +326,32 @@ __global__ void __launch_bounds__(256) k_ema_mean(float* __restrict__ grid, cons
         atomicAdd(sum + (blockIdx.x % kSumSlots) * kSumStride, (double)((wsum[0] + wsum[1]) + (wsum[2] + wsum[3])));
 }
 
+// The full sweep (indices == nullptr): every cell has exactly one new value, so `tmp` would be a permutation of `sigmas`
+// that k_ema_mean reads once -- read it in place instead.  float4 i of the grid is the Morton cells 4i .. 4i + 3 of one
+// cascade, a 2 x 2 block in x, y: the sweep's points cell + {0, 1, H, H + 1}.  Loop, launch geometry, the order of a thread's
+// sum and the `sum` slots are k_ema_mean's: the mean comes out bit for bit.
+__global__ void __launch_bounds__(256) k_ema_mean_sweep(float* __restrict__ grid, const float* __restrict__ sigmas,
+                                                        uint32_t total4, uint32_t H3, uint32_t logH, float scale,
+                                                        float decay, double* __restrict__ sum) {
+    __shared__ float wsum[4];
+    float acc = 0.0f;
+    for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < total4; i += gridDim.x * blockDim.x) {
+        const uint32_t c = i * 4, cas = c / H3, m = c - cas * H3;
+        const float* sp = sigmas + ((size_t)cas * H3 + compact_bits(m) + (compact_bits(m >> 1) << logH) +
+                                    (compact_bits(m >> 2) << (2 * logH)));
+        const float s0 = sp[0], s1 = sp[1], s2 = sp[(size_t)1 << logH], s3 = sp[((size_t)1 << logH) + 1];
+        float4 g = reinterpret_cast<float4*>(grid)[i];
+        g.x = ema1(g.x, s0 * scale, decay, acc); g.y = ema1(g.y, s1 * scale, decay, acc);
+        g.z = ema1(g.z, s2 * scale, decay, acc); g.w = ema1(g.w, s3 * scale, decay, acc);
+        reinterpret_cast<float4*>(grid)[i] = g;
+    }
+    for (int o = 32; o > 0; o >>= 1) acc += __shfl_down(acc, o, 64);
+    if (lane_id() == 0) wsum[threadIdx.x >> 6] = acc;
+    __syncthreads();
+    if (threadIdx.x == 0)
+        atomicAdd(sum + (blockIdx.x % kSumSlots) * kSumStride, (double)((wsum[0] + wsum[1]) + (wsum[2] + wsum[3])));
+}
+
 __global__ void __launch_bounds__(256) k_packbits_mean(const float* __restrict__ grid, uint32_t nbytes,
                                                        const double* __restrict__ sum, double inv_total,
                                                        float density_thresh, uint8_t* __restrict__ bitfield,
@@ -473,20 +499,26 @@ int enerf_density_grid_update(const int32_t* indices, const float* sigmas, uint3
     hipStream_t s = (hipStream_t)stream;
     const uint32_t H3 = H * H * H;
     const size_t cells = (size_t)C * H3;
+    if (!indices && n_per_cascade != H3) ENERF_BADARG("density_grid_update: indices may be NULL for a full sweep only");
     if (int ew = workspace_family_enter(1, s)) return ew;
-    char* ws = (char*)workspace(WS_DENSITY, kSumBytes + cells * 4);
+    // (the full sweep needs no `tmp`: k_ema_mean_sweep reads the densities where they are)
+    char* ws = (char*)workspace(WS_DENSITY, kSumBytes + (indices ? cells * 4 : 0));
     if (!ws) return ENERF_E_NOMEM;
     double* sum = (double*)ws;
-    float* tmp = (float*)(ws + kSumBytes);
     // (cleared by a launch of our own: a 2 KiB hipMemsetAsync takes a fill kernel of the runtime's that nothing else in
     // the step uses, and its first use in a process cost the first update 15-23 ms on a fresh box)
     k_zero_sums<<<1, kSumSlots * kSumStride, 0, s>>>(sum);
-    int e = check_hip(hipMemsetAsync(tmp, 0xFF, cells * 4, s), "density_grid_update: memset");   // NaN: "not evaluated"
-    if (e) return e;
-    const uint32_t P = n_per_cascade * C;
-    if (!indices && n_per_cascade != H3) ENERF_BADARG("density_grid_update: indices may be NULL for a full sweep only");
-    if (P) k_tmp_scatter<<<div_up(P, 256), 256, 0, s>>>(indices, sigmas, n_per_cascade, P, H3, sigma_scale, tmp, H, log2u(H));
-    k_ema_mean<<<2048, 256, 0, s>>>(density_grid, tmp, (uint32_t)(cells / 4), decay, sum);
+    if (!indices) {
+        k_ema_mean_sweep<<<2048, 256, 0, s>>>(density_grid, sigmas, (uint32_t)(cells / 4), H3, log2u(H), sigma_scale, decay,
+                                              sum);
+    } else {
+        float* tmp = (float*)(ws + kSumBytes);
+        int e = check_hip(hipMemsetAsync(tmp, 0xFF, cells * 4, s), "density_grid_update: memset");   // NaN: "not evaluated"
+        if (e) return e;
+        const uint32_t P = n_per_cascade * C;
+        if (P) k_tmp_scatter<<<div_up(P, 256), 256, 0, s>>>(indices, sigmas, n_per_cascade, P, H3, sigma_scale, tmp, H, log2u(H));
+        k_ema_mean<<<2048, 256, 0, s>>>(density_grid, tmp, (uint32_t)(cells / 4), decay, sum);
+    }
     const uint32_t nbytes = (uint32_t)(cells / 8);
     k_packbits_mean<<<div_up(nbytes, 256), 256, 0, s>>>(density_grid, nbytes, sum, 1.0 / (double)cells, density_thresh,
                                                         bitfield, step_counter, total_step, stats);

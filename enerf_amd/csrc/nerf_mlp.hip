@@ -131,13 +131,6 @@ struct NerfRows {                   // enerf_mlp32_valid_rows(_ex): see WSrc
     const int32_t* valid_rows;
     uint32_t valid_base, valid_cap;
 };
-__device__ __forceinline__ uint32_t nerf_valid_tiles(const NerfRows& r, uint32_t B, uint32_t ntiles) {
-    WSrc w;
-    w.valid_rows = r.valid_rows;
-    w.valid_base = r.valid_base;
-    w.valid_cap = r.valid_cap;
-    return valid_tiles(w, B, ntiles);
-}
 
 // the 16 SH values of a direction, those of the contraction slots of lane half h: slot e <-> component nrow(e, h)
 __device__ __forceinline__ void sh_slots(float d0, float d1, float d2, const ShNorm4& nrm, int h, float (&v)[8]) {
@@ -160,15 +153,51 @@ __device__ __forceinline__ void relu_tile(f32x16& a) {
 // count is a compile-time constant: as a plain load / store loop the copy cost one memory latency per iteration, twelve of
 // them in the forward's set-up)
 template <int COUNT>
-__device__ __forceinline__ void copy_frags(u32x4n* __restrict__ fr, const uint32_t* __restrict__ frags, int first, int slot0) {
+__device__ __forceinline__ void load_frags(u32x4n (&v)[COUNT * 128 / 256], const uint32_t* __restrict__ frags, int first) {
     const u32x4n* src = reinterpret_cast<const u32x4n*>(frags + (size_t)first * kFragWords);
+#pragma unroll
+    for (int k = 0; k < COUNT * 128 / 256; k++) v[k] = src[threadIdx.x + k * 256];
+}
+template <int COUNT>
+__device__ __forceinline__ void store_frags(u32x4n* __restrict__ fr, const u32x4n (&v)[COUNT * 128 / 256], int slot0) {
     u32x4n* dst = fr + slot0 * 128;
-    constexpr int N = COUNT * 128 / 256;
-    u32x4n v[N];
 #pragma unroll
-    for (int k = 0; k < N; k++) v[k] = src[threadIdx.x + k * 256];
+    for (int k = 0; k < COUNT * 128 / 256; k++) dst[threadIdx.x + k * 256] = v[k];
+}
+
+// The set-up of both kernels is ONE memory latency: the valid-row count, the first tile's inputs and the fragments are all
+// requested before anything waits, and whatever needs a loaded value -- the zeros of the rows past the batch, the count's
+// clamps, the LDS stores -- comes after the last request.  (As load_x, nerf_valid_tiles and the copy in a row the
+// compiled code drained each of the three before it issued the next: a select sat between the loads.)
+// the first tile's 16 inputs as loaded (load_x<1> without its zeros: rows s >= B of the padded batch are in bounds)
+__device__ __forceinline__ void request_x_raw(const float* __restrict__ X, uint32_t tile, int j, int h, uint32_t Bp,
+                                              float (&x)[16]) {
+    const size_t s = (size_t)tile * 32 + j;
 #pragma unroll
-    for (int k = 0; k < N; k++) dst[threadIdx.x + k * 256] = v[k];
+    for (int q = 0; q < 8; q++) {
+        const float2 t = *reinterpret_cast<const float2*>(X + ((size_t)(2 * q + h) * Bp + s) * 2);
+        x[2 * q] = t.x; x[2 * q + 1] = t.y;
+    }
+}
+__device__ __forceinline__ void finish_x_raw(uint32_t tile, int j, uint32_t B, float (&x)[16]) {
+    if (!((size_t)tile * 32 + j < B)) {
+#pragma unroll
+        for (int p = 0; p < 16; p++) x[p] = 0.0f;
+    }
+}
+// the count cell as every lane loads it (`safe`: any readable word, for the callers without a count) ...
+__device__ __forceinline__ int32_t request_valid_rows(const NerfRows& r, const uint32_t* __restrict__ safe) {
+    const int32_t* p = r.valid_rows ? r.valid_rows : reinterpret_cast<const int32_t*>(safe);
+    return *p;
+}
+// ... and nerf_valid_tiles of it, wave-uniform
+__device__ __forceinline__ uint32_t finish_valid_tiles(const NerfRows& r, int32_t raw, uint32_t B, uint32_t ntiles) {
+    if (!r.valid_rows) return ntiles;
+    int32_t v = __builtin_amdgcn_readfirstlane(raw);
+    if (r.valid_cap) v = (int32_t)r.valid_base + (v <= 0 ? 0 : (v < (int32_t)r.valid_cap ? v : (int32_t)r.valid_cap));
+    const uint32_t rows = v <= 0 ? 0u : ((uint32_t)v < B ? (uint32_t)v : B);
+    const uint32_t t = (rows + 31u) / 32u;
+    return t < ntiles ? t : ntiles;
 }
 
 // Residency.  Rounds 4-5 shipped this kernel with ONE workgroup per CU (84 KiB of LDS, the SIMD's whole register file
@@ -204,18 +233,26 @@ __global__ void __launch_bounds__(256) k_nerf_fwd(const float* __restrict__ X, c
     const uint32_t gw = blockIdx.x * 4 + (threadIdx.x >> 6);
     const uint32_t nw = gridDim.x * 4;
     float x[16];
-    if (gw < Bp / 32) load_x<1>(X, gw, j, h, B, Bp, x);           // (travels during the set-up)
+    const uint32_t t0 = gw < Bp / 32 ? gw : Bp / 32 - 1;          // (a wave without a tile loads the last one, unused)
     u32x4n* fr = reinterpret_cast<u32x4n*>(lds);
     typedef FragT<3> Frag;
-    copy_frags<NF_FWD>(fr, frags, 0, 0);
-    __syncthreads();
+    uint32_t ntiles;
+    {
+        u32x4n fv[NF_FWD * 128 / 256];
+        const int32_t rows_raw = request_valid_rows(rows, frags);
+        request_x_raw(X, t0, j, h, Bp, x);
+        load_frags<NF_FWD>(fv, frags, 0);
+        store_frags<NF_FWD>(fr, fv, 0);
+        __syncthreads();
+        ntiles = finish_valid_tiles(rows, rows_raw, B, Bp / 32);
+    }
+    finish_x_raw(t0, j, B, x);
     auto get = [&](int f) -> Frag {
         Frag w;
         w.hi = __builtin_bit_cast(bf16x8, fr[f * 128 + lane]);
         w.lo = __builtin_bit_cast(bf16x8, fr[f * 128 + 64 + lane]);
         return w;
     };
-    const uint32_t ntiles = nerf_valid_tiles(rows, B, Bp / 32);
     for (uint32_t tile = gw; tile < ntiles; tile += nw) {
         const size_t s = (size_t)tile * 32 + j;
         const bool valid = s < B;
@@ -373,10 +410,19 @@ __device__ __forceinline__ void mask_by_frag(f32x16& g, const FragT<3> (&f)[2]) 
 
 // The kernel's body; `lds`: the workgroup's kBwdLdsWords (FLIP_MFMA: operands, then the dW sums; selectors; stashes) or
 // kBwdLdsWordsTr (FLIP_LDS: operands; five images per wave) dwords.
-template <int TR>
+// How the four waves' weight-gradient accumulators become the workgroup's partial sum (w0 + w2) + (w1 + w3):
+//   TAIL_TWO_PHASE   : waves 0 / 1 store into a region each, barrier, waves 2 / 3 add into the same regions, barrier, one
+//                      pass adds the two regions (2 * P_STRIDE dwords of LDS: all the matrix-pipe form has to spare);
+//   TAIL_FOUR_REGIONS: every wave stores into a region of its own, barrier, one pass reads the four (16 bytes per lane and
+//                      region, every read of a thread issued before its first add) and adds them in the same association.
+enum { TAIL_TWO_PHASE = 0, TAIL_FOUR_REGIONS = 1 };
+template <int TR, int TAIL>
 __device__ __forceinline__ void nerf_bwd_body(uint32_t* lds, const NerfBwdArgs& a, const uint32_t* __restrict__ frags,
                                               const ShNorm4& nrm) {
     static_assert(NF_BWD * kFragWords >= 2 * P_STRIDE, "the two sum regions reuse the operand area");
+    static_assert(TAIL == TAIL_TWO_PHASE || (TR == FLIP_LDS && kBwdLdsWordsTr >= 4 * P_STRIDE),
+                  "four sum regions need 4 * P_STRIDE dwords: the LDS-transpose form's operands + images");
+    static_assert(P_STRIDE % 4 == 0 && (NW_S + HID * IN + HID * HID) % 4 == 0 && HID % 4 == 0, "16-byte reads of the sums");
     static_assert(kBwdLdsWords * 4 <= 160 * 1024 && kBwdLdsWordsTr * 4 <= 160 * 1024, "LDS");
 #if defined(MLP32S_NO_OPERAND_BARRIER)
     // nerf_mlp_bwd.hip compiles this kernel without the operand barrier: sound only while ONE workgroup of it fits a CU,
@@ -391,7 +437,6 @@ __device__ __forceinline__ void nerf_bwd_body(uint32_t* lds, const NerfBwdArgs& 
     const uint32_t B = a.B, out_c = a.out_c;
     const uint32_t Bp = (B + 31u) & ~31u;
     const uint32_t ntiles = Bp / 32;
-    const uint32_t nreal = nerf_valid_tiles(a.rows, B, ntiles);
     const uint32_t gw = blockIdx.x * 4 + wid;
     const uint32_t nw = gridDim.x * 4;
 
@@ -411,16 +456,22 @@ __device__ __forceinline__ void nerf_bwd_body(uint32_t* lds, const NerfBwdArgs& 
         ds_raw = a.g_sigma[sc];
         d0 = a.dirs[sc * 3]; d1 = a.dirs[sc * 3 + 1]; d2 = a.dirs[sc * 3 + 2];
     };
-    {
-        const uint32_t t0 = gw < ntiles ? gw : ntiles - 1;
-        request_x(t0);
-        request_out(t0);
-    }
     u32x4n* fr = reinterpret_cast<u32x4n*>(lds);
     u32x4n* sel = fr + NF_BWD * 128;                     // [kind][lane]
     u32x4n* stash = sel + 5 * 64 + wid * (kStashWords / 4);      // this wave's: [layer][block][K-step][hi, lo][lane]
-    copy_frags<20>(fr, frags, 0, 0);
-    copy_frags<20>(fr, frags, B_COT, 20);
+    // set-up: the count, the first tile's inputs (its index needs no count) and all 40 fragments are requested before the
+    // first wait -- the wave owns the SIMD's register file, the fragments sit in registers beside the tile's inputs
+    const uint32_t t0 = gw < ntiles ? gw : ntiles - 1;
+    const int32_t rows_raw = request_valid_rows(a.rows, frags);
+    request_x_raw(a.X, t0, j, h, Bp, x);
+    request_out(t0);
+    {
+        u32x4n fv0[10], fv1[10];
+        load_frags<20>(fv0, frags, 0);
+        load_frags<20>(fv1, frags, B_COT);
+        store_frags<20>(fr, fv0, 0);
+        store_frags<20>(fr, fv1, 20);
+    }
     if (TR == FLIP_MFMA && wid == 0) {
         // selection matrices of the flips: natural order (dL/dY), a tile's two register halves, and X^T (K-step t of the
         // input operand holds input columns kmap<1>(8t + e, h))
@@ -436,6 +487,8 @@ __device__ __forceinline__ void nerf_bwd_body(uint32_t* lds, const NerfBwdArgs& 
         }
     }
     __syncthreads();
+    const uint32_t nreal = finish_valid_tiles(a.rows, rows_raw, B, ntiles);      // the tile loop's bound and its skips
+    finish_x_raw(t0, j, B, x);
     auto get = [&](int f) -> Frag {                      // f: index in the global table
         const int slot = f < 20 ? f : f - 4;
         Frag w;
@@ -832,10 +885,10 @@ __device__ __forceinline__ void nerf_bwd_body(uint32_t* lds, const NerfBwdArgs& 
         }
     }
 
-    // per-workgroup sums in a fixed order (deterministic): waves 0 / 1 write their accumulators into a region each, waves
-    // 2 / 3 add into the same regions, then (w0 + w2) + (w1 + w3) leaves as this workgroup's partial sum
+    // per-workgroup sums in a fixed order (deterministic): (w0 + w2) + (w1 + w3) leaves as this workgroup's partial sum;
+    // the operands and the images are dead after this barrier
     __syncthreads();
-    float* red = reinterpret_cast<float*>(lds) + (size_t)(wid & 1) * P_STRIDE;
+    float* red = reinterpret_cast<float*>(lds) + (size_t)(TAIL == TAIL_FOUR_REGIONS ? wid : (wid & 1)) * P_STRIDE;
     const uint32_t NW_C = HID * IN + HID * HID + out_c * HID;
     auto flush = [&](const f32x16& acc, uint32_t base, int ld, int ob, int nb, uint32_t nrows, bool add) {
 #pragma unroll
@@ -861,24 +914,62 @@ __device__ __forceinline__ void nerf_bwd_body(uint32_t* lds, const NerfBwdArgs& 
 #pragma unroll
         for (int nb = 0; nb < 2; nb++) flush(awoC[nb], NW_S + HID * IN + HID * HID, HID, 0, nb, out_c, add);
     };
-    if (wid < 2) flush_all(false);
-    __syncthreads();
-    if (wid >= 2) flush_all(true);
-    __syncthreads();
     float* dst = a.partial + (size_t)blockIdx.x * P_STRIDE;
-    const float* r0 = reinterpret_cast<const float*>(lds);
-    for (uint32_t i = threadIdx.x; i < NW_S + NW_C; i += blockDim.x) dst[i] = r0[i] + r0[P_STRIDE + i];
+    if constexpr (TAIL == TAIL_FOUR_REGIONS) {
+        flush_all(false);
+        __syncthreads();
+        // thread i: float4 i, i + 256, ... of the sums -- its whole strip is read before the first add
+        constexpr uint32_t kStrip = (P_STRIDE / 4 + 255) / 256;
+        const uint32_t total4 = (NW_S + NW_C) / 4;
+        const float4* r = reinterpret_cast<const float4*>(lds);
+        float4 v[kStrip][4];
+#pragma unroll
+        for (uint32_t k = 0; k < kStrip; k++) {
+            const uint32_t i = threadIdx.x + k * 256;
+            if (i < total4) {
+#pragma unroll
+                for (uint32_t w = 0; w < 4; w++) v[k][w] = r[w * (P_STRIDE / 4) + i];
+            }
+        }
+#pragma unroll
+        for (uint32_t k = 0; k < kStrip; k++) {
+            const uint32_t i = threadIdx.x + k * 256;
+            if (i < total4) {
+                float4 o;
+                o.x = (v[k][0].x + v[k][2].x) + (v[k][1].x + v[k][3].x);
+                o.y = (v[k][0].y + v[k][2].y) + (v[k][1].y + v[k][3].y);
+                o.z = (v[k][0].z + v[k][2].z) + (v[k][1].z + v[k][3].z);
+                o.w = (v[k][0].w + v[k][2].w) + (v[k][1].w + v[k][3].w);
+                reinterpret_cast<float4*>(dst)[i] = o;
+            }
+        }
+    } else {
+        if (wid < 2) flush_all(false);
+        __syncthreads();
+        if (wid >= 2) flush_all(true);
+        __syncthreads();
+        const float* r0 = reinterpret_cast<const float*>(lds);
+        for (uint32_t i = threadIdx.x; i < NW_S + NW_C; i += blockDim.x) dst[i] = r0[i] + r0[P_STRIDE + i];
+    }
 }
 
 // The two forms as kernels: k_nerf_bwd transposes through LDS (the default), k_nerf_bwd_mfma on the matrix pipe (the form
 // shipped before; enerf_debug_nerf_bwd_transpose(0) selects it for A/B runs and for the bit-identity test).
+// The LDS form's 160 KiB hold four sum regions exactly; the matrix-pipe form's 149 KiB do not (it keeps the two-phase sums:
+// the comparator of tests/test_gpu_nerf_bwd_sums.py).  -DNERF_BWD_TWO_PHASE_TAIL: the default form with the two-phase sums,
+// for A/B timing only.
+#ifdef NERF_BWD_TWO_PHASE_TAIL
+constexpr int kBwdTail = TAIL_TWO_PHASE;
+#else
+constexpr int kBwdTail = TAIL_FOUR_REGIONS;
+#endif
 __global__ void __launch_bounds__(256) k_nerf_bwd(NerfBwdArgs a, const uint32_t* __restrict__ frags, ShNorm4 nrm) {
     __shared__ __attribute__((aligned(16))) uint32_t lds[kBwdLdsWordsTr];
-    nerf_bwd_body<FLIP_LDS>(lds, a, frags, nrm);
+    nerf_bwd_body<FLIP_LDS, kBwdTail>(lds, a, frags, nrm);
 }
 __global__ void __launch_bounds__(256) k_nerf_bwd_mfma(NerfBwdArgs a, const uint32_t* __restrict__ frags, ShNorm4 nrm) {
     __shared__ __attribute__((aligned(16))) uint32_t lds[kBwdLdsWords];
-    nerf_bwd_body<FLIP_MFMA>(lds, a, frags, nrm);
+    nerf_bwd_body<FLIP_MFMA, TAIL_TWO_PHASE>(lds, a, frags, nrm);
 }
 
 #endif
