@@ -31,19 +31,29 @@ SIGNATURES = {
     "enerf_march_rays_train_write": [_vp, _vp, _vp, _f32, _f32, _u32, _u32, _u32, _u32, _u32, _vp, _vp, _vp, _vp, _vp,
                                      _vp, _vp, _u32, _u32, _vp],
     "enerf_composite_rays_train_forward": [_vp, _vp, _vp, _vp, _u32, _u32, _vp, _vp, _vp, _vp],
+    "enerf_composite_rays_train_forward_c": [_vp, _vp, _vp, _vp, _u32, _u32, _vp, _vp, _vp, _u32, _vp],
     "enerf_composite_rays_train_forward_blend": [_vp, _vp, _vp, _vp, _u32, _u32, _vp, _vp, _vp, _vp, _u32, _f32, _vp,
                                                  _vp],
+    "enerf_composite_rays_train_forward_blend_c": [_vp, _vp, _vp, _vp, _u32, _u32, _vp, _vp, _vp, _vp, _u32, _f32, _vp,
+                                                 _u32, _vp],
     "enerf_composite_rays_train_backward_mse": [_vp, _vp, _f32, _vp, _u32, _f32, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
                                                 _u32, _u32, _vp, _vp, _vp, _vp],
+    "enerf_composite_rays_train_backward_mse_c": [_vp, _vp, _f32, _vp, _u32, _f32, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
+                                                _u32, _u32, _vp, _vp, _vp, _u32, _vp],
     "enerf_composite_rays_train_fwd_bwd_mse": [_vp, _vp, _vp, _vp, _u32, _u32, _vp, _vp, _vp, _u32, _f32, _vp, _vp, _f32,
                                                _vp, _vp, _vp, _vp, _vp],
+    "enerf_composite_rays_train_fwd_bwd_mse_c": [_vp, _vp, _vp, _vp, _u32, _u32, _vp, _vp, _vp, _u32, _f32, _vp, _vp, _f32,
+                                               _vp, _vp, _vp, _vp, _u32, _vp],
     "enerf_composite_rays_train_backward": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _u32, _u32, _vp, _vp, _vp],
+    "enerf_composite_rays_train_backward_c": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _u32, _u32, _vp, _vp, _u32, _vp],
     "enerf_composite_rays_frame": [_vp, _vp, _vp, _vp, _u32, _u32, _vp, _vp, _vp, _u32, _f32, _vp, _vp, _vp, _vp, _vp],
+    "enerf_composite_rays_frame_c": [_vp, _vp, _vp, _vp, _u32, _u32, _vp, _vp, _vp, _u32, _f32, _vp, _vp, _vp, _vp, _u32, _vp],
     "enerf_march_rays": [_u32, _u32, _vp, _vp, _vp, _vp, _f32, _f32, _u32, _u32, _u32, _vp, _vp, _vp, _vp, _vp,
                          _vp, _u32, _vp],
     "enerf_march_rays_ex": [_u32, _u32, _vp, _vp, _vp, _vp, _f32, _f32, _u32, _u32, _u32, _vp, _vp, _vp, _vp, _vp,
                             _vp, _u32, _u32, _vp],
     "enerf_composite_rays": [_u32, _u32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
+    "enerf_composite_rays_c": [_u32, _u32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _u32, _vp],
     "enerf_compact_rays": [_u32, _vp, _vp, _vp, _vp, _vp, _vp],
     "enerf_grid_encode_forward": [_vp, _vp, _vp, _vp, _u32, _u32, _u32, _u32, _f32, _u32, _int, _vp, _u32, _int,
                                   _int, _f32, _f32, _vp],
@@ -95,6 +105,7 @@ SIGNATURES = {
     "enerf_amp_cancel": [],
     "enerf_debug_march_thread_min_rays": [_u32],
     "enerf_event_loss_fwd_bwd": [_vp, _vp, _vp, _u32, _u32, _u32, _f32, _f32, _f32, _vp, _vp, _vp, _vp, _vp],
+    "enerf_event_loss_fwd_bwd_c": [_vp, _vp, _vp, _u32, _u32, _u32, _f32, _f32, _f32, _vp, _vp, _vp, _vp, _u32, _vp],
     "enerf_event_pair_rays": [_vp, _vp, _vp, _vp, _u32, _vp, _vp, _u32, _u32, _vp, _vp, _vp, _vp, _u32, _f32, _f32, _f32,
                               _f32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
     "enerf_event_single_pair_rays": [_vp, _u32, _vp, _vp, _u32, _vp, _vp, _u32, _vp, _vp, _vp, _vp, _u32, _f32, _f32, _f32,

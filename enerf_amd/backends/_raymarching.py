@@ -1,5 +1,6 @@
 """`_raymarching`: same 11 functions as raymarching/src/bindings.cpp:5-20 of the reference, same positional
-arguments, tensors pre-allocated by the caller; every call forwards to libenerf_hip.so on torch's current stream."""
+arguments, tensors pre-allocated by the caller; every call forwards to libenerf_hip.so on torch's current stream.
+The compositing calls take their channel count (1..3) from rgbs [.., C]; the reference's are three-channel."""
 from .. import _lib as L
 
 # inference samples marched since the last reset (bench.py: render Msamples/s)
@@ -30,6 +31,14 @@ def _u8(t, name):
         raise RuntimeError(f"{name} must be a uint8 tensor")
     L.check_contiguous(t, name)
     return t.data_ptr()
+
+
+def _channels(rgbs):
+    """Colour channels of a [.., C] colour tensor: the compositing kernels serve 1..3 (the reference's are three-channel)."""
+    C = int(rgbs.shape[-1]) if rgbs.dim() >= 2 else 0
+    if not 1 <= C <= 3:
+        raise ValueError(f"rgbs: expected [M,C] with 1..3 colour channels, got shape {tuple(rgbs.shape)}")
+    return C
 
 
 def near_far_from_aabb(rays_o, rays_d, aabb, N, min_near, nears, fars):
@@ -124,77 +133,81 @@ def march_rays_train_write(rays_o, rays_d, grid, bound, dt_gamma, max_steps, N, 
 def composite_rays_frame(sigmas, rgbs, deltas, rays, N, M, nears, fars, bg_color, weights_sum, depth, image,
                          used_samples=None):
     """Whole-frame inference compositing over contiguously marched samples (include/enerf_hip.h)."""
-    bg, stride, scalar = _background(bg_color, N)
-    L.check(L.lib().enerf_composite_rays_frame(
+    C = _channels(rgbs)
+    bg, stride, scalar = _background(bg_color, N, C)
+    L.check(L.lib().enerf_composite_rays_frame_c(
         _f32(sigmas, "sigmas"), _f32(rgbs, "rgbs"), _f32(deltas, "deltas"), _i32(rays, "rays"), int(N), int(M),
         _f32(nears, "nears"), _f32(fars, "fars"), bg, stride, scalar, _f32(weights_sum, "weights_sum"),
-        _f32(depth, "depth"), _f32(image, "image"), None if used_samples is None else used_samples.data_ptr(),
+        _f32(depth, "depth"), _f32(image, "image"), None if used_samples is None else used_samples.data_ptr(), C,
         L.stream_handle()), "composite_rays_frame")
 
 
-def _background(bg_color, N):
-    """-> (pointer, stride, scalar) of the C ABI's background triple."""
+def _background(bg_color, N, C=3):
+    """-> (pointer, stride, scalar) of the C ABI's background triple, for images of C channels."""
     import torch
     if isinstance(bg_color, torch.Tensor):
         if bg_color.numel() == 1:
             return None, 0, float(bg_color)
         bg = _f32(bg_color, "bg_color")
-        if bg_color.numel() == 3:
+        if bg_color.numel() == C:
             return bg, 0, 0.0
-        if bg_color.numel() == 3 * N:
-            return bg, 3, 0.0
-        raise ValueError(f"bg_color: expected 1, 3 or {3 * N} elements, got {bg_color.numel()}")
+        if bg_color.numel() == C * N:
+            return bg, C, 0.0
+        raise ValueError(f"bg_color: expected 1, {C} or {C * N} elements, got {bg_color.numel()}")
     return None, 0, float(bg_color)
 
 
 def composite_rays_train_forward_blend(sigmas, rgbs, deltas, rays, M, N, weights_sum, depth, image, bg_color,
                                        out_image):
-    bg, stride, scalar = _background(bg_color, N)
-    L.check(L.lib().enerf_composite_rays_train_forward_blend(
+    C = _channels(rgbs)
+    bg, stride, scalar = _background(bg_color, N, C)
+    L.check(L.lib().enerf_composite_rays_train_forward_blend_c(
         _f32(sigmas, "sigmas"), _f32(rgbs, "rgbs"), _f32(deltas, "deltas"), _i32(rays, "rays"), int(M), int(N),
         _f32(weights_sum, "weights_sum"), None if depth is None else _f32(depth, "depth"), _f32(image, "image"), bg,
-        stride, scalar, _f32(out_image, "out_image"), L.stream_handle()), "composite_rays_train_forward_blend")
+        stride, scalar, _f32(out_image, "out_image"), C, L.stream_handle()), "composite_rays_train_forward_blend")
 
 
 def composite_rays_train_backward_mse(out_image, target, grad_scale, bg_color, counter, sigmas, rgbs, deltas, rays,
                                       weights_sum, image, M, N, grad_sigmas, grad_rgbs, loss=None):
-    bg, stride, scalar = _background(bg_color, N)
-    L.check(L.lib().enerf_composite_rays_train_backward_mse(
+    C = _channels(rgbs)
+    bg, stride, scalar = _background(bg_color, N, C)
+    L.check(L.lib().enerf_composite_rays_train_backward_mse_c(
         _f32(out_image, "out_image"), None if target is None else _f32(target, "target"), float(grad_scale), bg,
         stride, scalar,
         _i32(counter, "counter"), _f32(sigmas, "sigmas"), _f32(rgbs, "rgbs"), _f32(deltas, "deltas"),
         _i32(rays, "rays"), _f32(weights_sum, "weights_sum"), _f32(image, "image"), int(M), int(N),
         _f32(grad_sigmas, "grad_sigmas"), _f32(grad_rgbs, "grad_rgbs"),
-        None if loss is None else _f32(loss, "loss"), L.stream_handle()), "composite_rays_train_backward_mse")
+        None if loss is None else _f32(loss, "loss"), C, L.stream_handle()), "composite_rays_train_backward_mse")
 
 
 def composite_rays_train_fwd_bwd_mse(sigmas, rgbs, deltas, rays, M, N, weights_sum, image, bg_color, out_image, target,
                                      grad_scale, counter, grad_sigmas, grad_rgbs, loss=None):
     """forward_blend + backward_mse(target) in one launch (include/enerf_hip.h)."""
-    bg, stride, scalar = _background(bg_color, N)
-    L.check(L.lib().enerf_composite_rays_train_fwd_bwd_mse(
+    C = _channels(rgbs)
+    bg, stride, scalar = _background(bg_color, N, C)
+    L.check(L.lib().enerf_composite_rays_train_fwd_bwd_mse_c(
         _f32(sigmas, "sigmas"), _f32(rgbs, "rgbs"), _f32(deltas, "deltas"), _i32(rays, "rays"), int(M), int(N),
         _f32(weights_sum, "weights_sum"), _f32(image, "image"), bg, stride, scalar, _f32(out_image, "out_image"),
         _f32(target, "target"), float(grad_scale), _i32(counter, "counter"), _f32(grad_sigmas, "grad_sigmas"),
-        _f32(grad_rgbs, "grad_rgbs"), None if loss is None else _f32(loss, "loss"), L.stream_handle()),
+        _f32(grad_rgbs, "grad_rgbs"), None if loss is None else _f32(loss, "loss"), C, L.stream_handle()),
         "composite_rays_train_fwd_bwd_mse")
 
 
 def composite_rays_train_forward(sigmas, rgbs, deltas, rays, M, N, weights_sum, depth, image):
-    L.check(L.lib().enerf_composite_rays_train_forward(_f32(sigmas, "sigmas"), _f32(rgbs, "rgbs"),
-                                                       _f32(deltas, "deltas"), _i32(rays, "rays"), int(M), int(N),
-                                                       _f32(weights_sum, "weights_sum"), _f32(depth, "depth"),
-                                                       _f32(image, "image"), L.stream_handle()),
+    L.check(L.lib().enerf_composite_rays_train_forward_c(_f32(sigmas, "sigmas"), _f32(rgbs, "rgbs"),
+                                                         _f32(deltas, "deltas"), _i32(rays, "rays"), int(M), int(N),
+                                                         _f32(weights_sum, "weights_sum"), _f32(depth, "depth"),
+                                                         _f32(image, "image"), _channels(rgbs), L.stream_handle()),
             "composite_rays_train_forward")
 
 
 def composite_rays_train_backward(grad_weights_sum, grad_image, sigmas, rgbs, deltas, rays, weights_sum, image, M, N,
                                   grad_sigmas, grad_rgbs):
-    L.check(L.lib().enerf_composite_rays_train_backward(
+    L.check(L.lib().enerf_composite_rays_train_backward_c(
         _f32(grad_weights_sum, "grad_weights_sum"), _f32(grad_image, "grad_image"), _f32(sigmas, "sigmas"),
         _f32(rgbs, "rgbs"), _f32(deltas, "deltas"), _i32(rays, "rays"), _f32(weights_sum, "weights_sum"),
         _f32(image, "image"), int(M), int(N), _f32(grad_sigmas, "grad_sigmas"), _f32(grad_rgbs, "grad_rgbs"),
-        L.stream_handle()), "composite_rays_train_backward")
+        _channels(rgbs), L.stream_handle()), "composite_rays_train_backward")
 
 
 def march_rays_ex(n_alive, n_step, rays_alive, rays_t, rays_o, rays_d, bound, dt_gamma, max_steps, C, H, grid, nears,
@@ -223,11 +236,11 @@ def march_rays(n_alive, n_step, rays_alive, rays_t, rays_o, rays_d, bound, dt_ga
 
 
 def composite_rays(n_alive, n_step, rays_alive, rays_t, sigmas, rgbs, deltas, weights_sum, depth, image):
-    L.check(L.lib().enerf_composite_rays(int(n_alive), int(n_step), _i32(rays_alive, "rays_alive"),
-                                         _f32(rays_t, "rays_t"), _f32(sigmas, "sigmas"), _f32(rgbs, "rgbs"),
-                                         _f32(deltas, "deltas"), _f32(weights_sum, "weights_sum"),
-                                         _f32(depth, "depth"), _f32(image, "image"), L.stream_handle()),
-            "composite_rays")
+    L.check(L.lib().enerf_composite_rays_c(int(n_alive), int(n_step), _i32(rays_alive, "rays_alive"),
+                                           _f32(rays_t, "rays_t"), _f32(sigmas, "sigmas"), _f32(rgbs, "rgbs"),
+                                           _f32(deltas, "deltas"), _f32(weights_sum, "weights_sum"),
+                                           _f32(depth, "depth"), _f32(image, "image"), _channels(rgbs),
+                                           L.stream_handle()), "composite_rays")
 
 
 def compact_rays(n_alive, rays_alive, rays_alive_old, rays_t, rays_t_old, alive_counter):

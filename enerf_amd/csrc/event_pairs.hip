@@ -138,7 +138,7 @@ __global__ void __launch_bounds__(256) k_no_event_rays(
 // ---- event loss, forward and gradient in one launch (nerf/utils.py:499-516 with C_thres != -1) ------------------------
 // Per ray: (luma of) the two renders -> lin-log / log intensities -> delta = p2 - p1 -> (delta - pol * C)^2, mean over
 // rays x channels.  Writes delta, d loss / d image1, d loss / d image2 and the loss (one workgroup, fixed summation
-// order).  The arithmetic follows events.py (= utils/event_utils.py:23-66) operation by operation.
+// order).  CH = channels of the images (1..3); luma is a three-channel operation.  The arithmetic follows events.py (= utils/event_utils.py:23-66) operation by operation.
 struct EventLossCfg {
     uint32_t use_luma, linlog;
     float c_thres, log_thres, upstream;
@@ -159,20 +159,21 @@ __device__ __forceinline__ void ev_intensity(float l, const EventLossCfg& c, flo
         else { p = logf(c.log_thres); dp = 0.0f; }
     }
 }
+template <int CH>
 __global__ void __launch_bounds__(1024) k_event_loss(const float* __restrict__ img1, const float* __restrict__ img2,
                                                      const float* __restrict__ pols, uint32_t N, EventLossCfg c,
                                                      float* __restrict__ g1, float* __restrict__ g2,
                                                      float* __restrict__ delta, float* __restrict__ loss) {
     __shared__ double red[1024];
-    const uint32_t ch = c.use_luma ? 1u : 3u;
+    const uint32_t ch = (CH == 3 && c.use_luma) ? 1u : (uint32_t)CH;
     const float inv_count = 1.0f / (float)(N * ch);
     double acc = 0.0;
     for (uint32_t r = threadIdx.x; r < N; r += 1024u) {
-        const float* a = img1 + (size_t)r * 3;
-        const float* b = img2 + (size_t)r * 3;
+        const float* a = img1 + (size_t)r * CH;
+        const float* b = img2 + (size_t)r * CH;
         const float target = pols[r] * c.c_thres;
         float ga[3] = {0.f, 0.f, 0.f}, gb[3] = {0.f, 0.f, 0.f};
-        if (c.use_luma) {
+        if (CH == 3 && c.use_luma) {
             float p1, d1, p2, d2;
             ev_intensity(ev_luma(a), c, p1, d1);
             // without lin-log the reference evaluates the second term on the FIRST luma (nerf/utils.py:500): delta = 0
@@ -187,21 +188,21 @@ __global__ void __launch_bounds__(1024) k_event_loss(const float* __restrict__ i
                 else ga[k] = (gd * d2 - gd * d1) * w[k];
             }
         } else {
-            for (int k = 0; k < 3; k++) {
+            for (int k = 0; k < CH; k++) {
                 float p1, d1, p2, d2;
                 ev_intensity(a[k], c, p1, d1);
                 ev_intensity(b[k], c, p2, d2);
                 const float dl = p2 - p1, res = dl - target;
-                delta[(size_t)r * 3 + k] = dl;
+                delta[(size_t)r * CH + k] = dl;
                 acc += (double)(res * res);
                 const float gd = c.upstream * (2.0f * res * inv_count);
                 ga[k] = -gd * d1;
                 gb[k] = gd * d2;
             }
         }
-        for (int k = 0; k < 3; k++) {
-            g1[(size_t)r * 3 + k] = ga[k];
-            g2[(size_t)r * 3 + k] = gb[k];
+        for (int k = 0; k < CH; k++) {
+            g1[(size_t)r * CH + k] = ga[k];
+            g2[(size_t)r * CH + k] = gb[k];
         }
     }
     red[threadIdx.x] = acc;
@@ -275,12 +276,28 @@ extern "C" int enerf_event_loss_fwd_bwd(const float* image1, const float* image2
                                         uint32_t use_luma, uint32_t linlog, float C_thres, float log_thres, float upstream,
                                         float* grad_image1, float* grad_image2, float* delta, float* loss,
                                         enerf_stream_t stream) {
+    return enerf_event_loss_fwd_bwd_c(image1, image2, pols, N, use_luma, linlog, C_thres, log_thres, upstream, grad_image1,
+                                      grad_image2, delta, loss, 3, stream);
+}
+
+extern "C" int enerf_event_loss_fwd_bwd_c(const float* image1, const float* image2, const float* pols, uint32_t N,
+                                          uint32_t use_luma, uint32_t linlog, float C_thres, float log_thres, float upstream,
+                                          float* grad_image1, float* grad_image2, float* delta, float* loss,
+                                          uint32_t channels, enerf_stream_t stream) {
+    if (channels < 1u || channels > 3u) ENERF_BADARG("event_loss_fwd_bwd: %u colour channels (1..3 are served)", channels);
+    if (use_luma && channels != 3u)
+        ENERF_BADARG("event_loss_fwd_bwd: luma is a three-channel operation (%u channels given)", channels);
     if (N == 0) return 0;
     if (!image1 || !image2 || !pols || !grad_image1 || !grad_image2 || !delta)
         ENERF_BADARG("event_loss_fwd_bwd: images, pols, gradients and delta are required");
     if (C_thres == -1.0f) ENERF_BADARG("event_loss_fwd_bwd: the normalised loss (C_thres == -1) is not fused");
     const EventLossCfg c = {use_luma, linlog, C_thres, log_thres, upstream};
-    k_event_loss<<<1, 1024, 0, (hipStream_t)stream>>>(image1, image2, pols, N, c, grad_image1, grad_image2, delta, loss);
+    if (channels == 1u)
+        k_event_loss<1><<<1, 1024, 0, (hipStream_t)stream>>>(image1, image2, pols, N, c, grad_image1, grad_image2, delta, loss);
+    else if (channels == 2u)
+        k_event_loss<2><<<1, 1024, 0, (hipStream_t)stream>>>(image1, image2, pols, N, c, grad_image1, grad_image2, delta, loss);
+    else
+        k_event_loss<3><<<1, 1024, 0, (hipStream_t)stream>>>(image1, image2, pols, N, c, grad_image1, grad_image2, delta, loss);
     ENERF_LAUNCH_CHECK("event_loss_fwd_bwd");
     return 0;
 }

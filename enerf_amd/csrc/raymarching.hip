@@ -397,16 +397,31 @@ __global__ void __launch_bounds__(64) k_march_write(const float* __restrict__ ra
 }
 
 // ------------------------------------------------------------------ composite_rays_train (one wavefront per ray)
-// Lanes take consecutive samples (coalesced 4/8/12-byte-per-lane loads); transmittance is a wave prefix
+// Lanes take consecutive samples (coalesced 4/8/4C-byte-per-lane loads); transmittance is a wave prefix
 // product, the running sums are wave prefix sums, chunk to chunk carries live in every lane.
+// C = colour channels (1..3: the colour net's output width); one colour scan per channel.
+// FOR_CH(q, statement): the statement once per channel q = 0 .. C-1, expanded where it stands (straight-line code, as if
+// written out by hand: the three-channel kernels compile to what their hand-written form compiled to)
+#define FOR_CH(q, ...)                                            \
+    { constexpr int q = 0; __VA_ARGS__; }                         \
+    if constexpr (C > 1) { constexpr int q = 1; __VA_ARGS__; }    \
+    if constexpr (C > 2) { constexpr int q = 2; __VA_ARGS__; }
+template <int C>
 struct CompCarry {
-    float T, t, r, g, b, ws, d;
+    float T, t, c[C], ws, d;
+    __device__ __forceinline__ CompCarry() {
+        T = 1.0f;
+        t = 0.0f;
+        FOR_CH(q, c[q] = 0.0f);
+        ws = 0.0f;
+        d = 0.0f;
+    }
 };
 
 // Processes one chunk of <= 64 samples; returns per-lane inclusive quantities and updates the carry.
-__device__ __forceinline__ void comp_chunk(bool active, float sigma, float dl0, float dl1, float c0, float c1,
-                                           float c2, int lane, CompCarry& k, float& w, float& T_post, float& r_i,
-                                           float& g_i, float& b_i, float& ws_i) {
+template <int C>
+__device__ __forceinline__ void comp_chunk(bool active, float sigma, float dl0, float dl1, const float (&c)[C], int lane,
+                                           CompCarry<C>& k, float& w, float& T_post, float (&c_i)[C], float& ws_i) {
     const float alpha = active ? 1.0f - __expf(-sigma * dl0) : 0.0f;
     const float om = 1.0f - alpha;
     const float P = wave_incl_scan_mul(om, lane);  // prod_{j<=i} (1 - alpha_j) within the chunk
@@ -414,22 +429,18 @@ __device__ __forceinline__ void comp_chunk(bool active, float sigma, float dl0, 
     w = alpha * (k.T * Pex);
     T_post = k.T * P;
     const float tt = k.t + wave_incl_scan_add(active ? dl1 : 0.0f, lane);
-    r_i = k.r + wave_incl_scan_add(w * c0, lane);
-    g_i = k.g + wave_incl_scan_add(w * c1, lane);
-    b_i = k.b + wave_incl_scan_add(w * c2, lane);
+    FOR_CH(q, c_i[q] = k.c[q] + wave_incl_scan_add(w * c[q], lane));
     ws_i = k.ws + wave_incl_scan_add(w, lane);
     const float d_i = k.d + wave_incl_scan_add(w * tt, lane);
     k.T = wave_bcast(T_post, 63);
     k.t = wave_bcast(tt, 63);
-    k.r = wave_bcast(r_i, 63);
-    k.g = wave_bcast(g_i, 63);
-    k.b = wave_bcast(b_i, 63);
+    FOR_CH(q, k.c[q] = wave_bcast(c_i[q], 63));
     k.ws = wave_bcast(ws_i, 63);
     k.d = wave_bcast(d_i, 63);
 }
 
-// background colour of the blend `image + (1 - weights_sum) * bg`: a scalar (color == nullptr), one RGB (stride 0) or one
-// RGB per ray (stride 3)
+// background colour of the blend `image + (1 - weights_sum) * bg`: a scalar (color == nullptr), one colour of C channels
+// (stride 0) or one per ray (stride C)
 struct Background {
     const float* color;
     uint32_t stride;
@@ -439,6 +450,7 @@ struct Background {
     }
 };
 
+template <int C>
 __global__ void __launch_bounds__(256) k_composite_train_fwd(const float* __restrict__ sigmas,
                                                              const float* __restrict__ rgbs,
                                                              const float* __restrict__ deltas,
@@ -454,39 +466,53 @@ __global__ void __launch_bounds__(256) k_composite_train_fwd(const float* __rest
         if (lane == 0) {
             weights_sum[index] = 0;
             if (depth) depth[index] = 0;
-            image[(size_t)index * 3] = 0; image[(size_t)index * 3 + 1] = 0; image[(size_t)index * 3 + 2] = 0;
+            FOR_CH(q, image[(size_t)index * C + q] = 0);
             if (out_image) {
-                out_image[(size_t)index * 3] = bg.at(index, 0);
-                out_image[(size_t)index * 3 + 1] = bg.at(index, 1);
-                out_image[(size_t)index * 3 + 2] = bg.at(index, 2);
+                FOR_CH(q, out_image[(size_t)index * C + q] = bg.at(index, q));
             }
         }
         return;
     }
-    CompCarry k = {1.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
+    CompCarry<C> k;
     for (uint32_t s0 = 0; s0 < num_steps; s0 += 64) {
         const uint32_t s = s0 + lane;
         const bool active = s < num_steps;
         const size_t p = (size_t)offset + (active ? s : 0);
         const float sigma = sigmas[p];
         const float2 dl = reinterpret_cast<const float2*>(deltas)[p];
-        const float c0 = rgbs[p * 3], c1 = rgbs[p * 3 + 1], c2 = rgbs[p * 3 + 2];
-        float w, T_post, r_i, g_i, b_i, ws_i;
-        comp_chunk(active, sigma, dl.x, dl.y, c0, c1, c2, lane, k, w, T_post, r_i, g_i, b_i, ws_i);
+        float c[C];
+        FOR_CH(q, c[q] = rgbs[p * C + q]);
+        float w, T_post, c_i[C], ws_i;
+        comp_chunk<C>(active, sigma, dl.x, dl.y, c, lane, k, w, T_post, c_i, ws_i);
     }
     if (lane == 0) {
         weights_sum[index] = k.ws;
         if (depth) depth[index] = k.d;
-        image[(size_t)index * 3] = k.r; image[(size_t)index * 3 + 1] = k.g; image[(size_t)index * 3 + 2] = k.b;
+        FOR_CH(q, image[(size_t)index * C + q] = k.c[q]);
         if (out_image) {
             // image + (1 - weights_sum) * bg_color, in torch's operation order (nerf/renderer.py:352)
             const float rest = 1.0f - k.ws;
             // (separately rounded multiply and add: bit-identical to the elementwise route, no fma contraction)
-            out_image[(size_t)index * 3] = __fadd_rn(k.r, __fmul_rn(rest, bg.at(index, 0)));
-            out_image[(size_t)index * 3 + 1] = __fadd_rn(k.g, __fmul_rn(rest, bg.at(index, 1)));
-            out_image[(size_t)index * 3 + 2] = __fadd_rn(k.b, __fmul_rn(rest, bg.at(index, 2)));
+            FOR_CH(q, out_image[(size_t)index * C + q] = __fadd_rn(k.c[q], __fmul_rn(rest, bg.at(index, q))));
         }
     }
+}
+
+// g . bg and sum_q g_q (T c_q - (final_q - incl_q)), summed left to right from channel 0
+template <int C>
+__device__ __forceinline__ float bg_dot(const float (&g)[C], const Background& bg, uint32_t ray) {
+    if constexpr (C == 1) return g[0] * bg.at(ray, 0);
+    else if constexpr (C == 2) return g[0] * bg.at(ray, 0) + g[1] * bg.at(ray, 1);
+    else return g[0] * bg.at(ray, 0) + g[1] * bg.at(ray, 1) + g[2] * bg.at(ray, 2);
+}
+template <int C>
+__device__ __forceinline__ float colour_terms(const float (&g)[C], float T, const float (&c)[C], const float (&c_final)[C],
+                                              const float (&c_i)[C]) {
+    if constexpr (C == 1) return g[0] * (T * c[0] - (c_final[0] - c_i[0]));
+    else if constexpr (C == 2) return g[0] * (T * c[0] - (c_final[0] - c_i[0])) + g[1] * (T * c[1] - (c_final[1] - c_i[1]));
+    else
+        return g[0] * (T * c[0] - (c_final[0] - c_i[0])) + g[1] * (T * c[1] - (c_final[1] - c_i[1])) +
+               g[2] * (T * c[2] - (c_final[2] - c_i[2]));
 }
 
 // the fused form of the backward: gradient of an MSE loss on the blended image, computed in place of reading it
@@ -501,7 +527,7 @@ struct MseTail {
     const float* scale_mul; // optional (enerf_amp_begin): the gradient -- not the reported loss -- is multiplied by *scale_mul
 };
 
-template <bool MSE>
+template <bool MSE, int C>
 __global__ void __launch_bounds__(MSE ? 1024 : 256) k_composite_train_bwd(
     const float* __restrict__ grad_weights_sum, const float* __restrict__ grad_image,
     const float* __restrict__ sigmas, const float* __restrict__ rgbs, const float* __restrict__ deltas,
@@ -513,7 +539,7 @@ __global__ void __launch_bounds__(MSE ? 1024 : 256) k_composite_train_bwd(
         const uint32_t tid = (blockIdx.x - ray_blocks) * blockDim.x + threadIdx.x;
         const uint32_t nth = (gridDim.x - ray_blocks) * blockDim.x;
         for (size_t i = (size_t)used + tid; i < (size_t)M; i += nth) grad_sigmas[i] = 0.0f;
-        for (size_t i = (size_t)used * 3 + tid; i < (size_t)M * 3; i += nth) grad_rgbs[i] = 0.0f;
+        for (size_t i = (size_t)used * C + tid; i < (size_t)M * C; i += nth) grad_rgbs[i] = 0.0f;
         return;
     }
     const uint32_t n = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
@@ -521,12 +547,12 @@ __global__ void __launch_bounds__(MSE ? 1024 : 256) k_composite_train_bwd(
         // the loss value itself, for whoever logs it: every ray contributes, marched or not
         __shared__ float s_err[16];
         float e = 0.0f;
-        if (n < N && lane_id() < 3) {
+        if (n < N && lane_id() < C) {
             const uint32_t ray = (uint32_t)rays[(size_t)n * 3];
-            const float d = mse.out_image[(size_t)ray * 3 + lane_id()] - mse.target[(size_t)ray * 3 + lane_id()];
+            const float d = mse.out_image[(size_t)ray * C + lane_id()] - mse.target[(size_t)ray * C + lane_id()];
             e = d * d;
         }
-        e += dpp_take<0x102>(0.0f, e);                        // lanes 0..2 -> lane 0 (row_shl 2, 1)
+        e += dpp_take<0x102>(0.0f, e);                        // lanes 0..2 -> lane 0 (row_shl 2, 1); lanes >= C hold 0
         e += dpp_take<0x101>(0.0f, e);
         if (lane_id() == 0) s_err[threadIdx.x >> 6] = e;
         __syncthreads();
@@ -543,49 +569,43 @@ __global__ void __launch_bounds__(MSE ? 1024 : 256) k_composite_train_bwd(
     if (num_steps == 0 || offset + num_steps >= M) {
         if (MSE && num_steps != 0 && offset < M) {          // a dropped ray's reservation, clipped to the buffer
             for (size_t i = (size_t)offset + lane; i < (size_t)M; i += 64) grad_sigmas[i] = 0.0f;
-            for (size_t i = (size_t)offset * 3 + lane; i < (size_t)M * 3; i += 64) grad_rgbs[i] = 0.0f;
+            for (size_t i = (size_t)offset * C + lane; i < (size_t)M * C; i += 64) grad_rgbs[i] = 0.0f;
         }
         return;
     }
-    float gws, gi0, gi1, gi2;
+    float gws, gi[C];
     if (MSE) {
-        // loss = mean((out_image - target)^2): d/d(out_image) = (out_image - target) * scale, scale = 2 / (3 N) * upstream;
+        // loss = mean((out_image - target)^2): d/d(out_image) = (out_image - target) * scale, scale = 2 / (C N) * upstream;
         // out_image = image + (1 - weights_sum) * bg  ->  d/d(weights_sum) = -(g . bg)
         // (target == nullptr: out_image already holds d loss / d out_image of some other loss)
-        gi0 = mse.out_image[(size_t)index * 3], gi1 = mse.out_image[(size_t)index * 3 + 1];
-        gi2 = mse.out_image[(size_t)index * 3 + 2];
+        FOR_CH(q, gi[q] = mse.out_image[(size_t)index * C + q]);
         if (mse.target) {
-            gi0 -= mse.target[(size_t)index * 3];
-            gi1 -= mse.target[(size_t)index * 3 + 1];
-            gi2 -= mse.target[(size_t)index * 3 + 2];
+            FOR_CH(q, gi[q] -= mse.target[(size_t)index * C + q]);
         }
         const float gsc = mse.scale_mul ? mse.scale * mse.scale_mul[0] : mse.scale;
-        gi0 *= gsc; gi1 *= gsc; gi2 *= gsc;
-        gws = -(gi0 * mse.bg.at(index, 0) + gi1 * mse.bg.at(index, 1) + gi2 * mse.bg.at(index, 2));
+        FOR_CH(q, gi[q] *= gsc);
+        gws = -bg_dot<C>(gi, mse.bg, index);
     } else {
         gws = grad_weights_sum[index];
-        gi0 = grad_image[(size_t)index * 3]; gi1 = grad_image[(size_t)index * 3 + 1];
-        gi2 = grad_image[(size_t)index * 3 + 2];
+        FOR_CH(q, gi[q] = grad_image[(size_t)index * C + q]);
     }
-    const float r_final = image[(size_t)index * 3], g_final = image[(size_t)index * 3 + 1],
-                b_final = image[(size_t)index * 3 + 2];
+    float c_final[C];
+    FOR_CH(q, c_final[q] = image[(size_t)index * C + q]);
     const float ws_final = weights_sum[index];
-    CompCarry k = {1.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
+    CompCarry<C> k;
     for (uint32_t s0 = 0; s0 < num_steps; s0 += 64) {
         const uint32_t s = s0 + lane;
         const bool active = s < num_steps;
         const size_t p = (size_t)offset + (active ? s : 0);
         const float sigma = sigmas[p];
         const float2 dl = reinterpret_cast<const float2*>(deltas)[p];
-        const float c0 = rgbs[p * 3], c1 = rgbs[p * 3 + 1], c2 = rgbs[p * 3 + 2];
-        float w, T, r_i, g_i, b_i, ws_i;
-        comp_chunk(active, sigma, dl.x, dl.y, c0, c1, c2, lane, k, w, T, r_i, g_i, b_i, ws_i);
+        float c[C];
+        FOR_CH(q, c[q] = rgbs[p * C + q]);
+        float w, T, c_i[C], ws_i;
+        comp_chunk<C>(active, sigma, dl.x, dl.y, c, lane, k, w, T, c_i, ws_i);
         if (active) {
-            grad_rgbs[p * 3] = gi0 * w;
-            grad_rgbs[p * 3 + 1] = gi1 * w;
-            grad_rgbs[p * 3 + 2] = gi2 * w;
-            grad_sigmas[p] = dl.x * (gi0 * (T * c0 - (r_final - r_i)) + gi1 * (T * c1 - (g_final - g_i)) +
-                                     gi2 * (T * c2 - (b_final - b_i)) + gws * (T - (ws_final - ws_i)));
+            FOR_CH(q, grad_rgbs[p * C + q] = gi[q] * w);
+            grad_sigmas[p] = dl.x * (colour_terms<C>(gi, T, c, c_final, c_i) + gws * (T - (ws_final - ws_i)));
         }
     }
 }
@@ -594,6 +614,7 @@ __global__ void __launch_bounds__(MSE ? 1024 : 256) k_composite_train_bwd(
 // training step needs nothing between the two compositing kernels, so the second pass over the ray's samples follows
 // the first while they are still in L2, image / weights_sum stay in registers, and one launch (and the gap before it)
 // disappears.  Same arithmetic, in the same order, as k_composite_train_fwd + k_composite_train_bwd<true>.
+template <int C>
 __global__ void __launch_bounds__(1024) k_composite_train_fwd_bwd_mse(
     const float* __restrict__ sigmas, const float* __restrict__ rgbs, const float* __restrict__ deltas,
     const int32_t* __restrict__ rays, uint32_t M, uint32_t N, float* weights_sum, float* image, float* out_image,
@@ -603,7 +624,7 @@ __global__ void __launch_bounds__(1024) k_composite_train_fwd_bwd_mse(
         const uint32_t tid = (blockIdx.x - ray_blocks) * blockDim.x + threadIdx.x;
         const uint32_t nth = (gridDim.x - ray_blocks) * blockDim.x;
         for (size_t i = (size_t)used + tid; i < (size_t)M; i += nth) grad_sigmas[i] = 0.0f;
-        for (size_t i = (size_t)used * 3 + tid; i < (size_t)M * 3; i += nth) grad_rgbs[i] = 0.0f;
+        for (size_t i = (size_t)used * C + tid; i < (size_t)M * C; i += nth) grad_rgbs[i] = 0.0f;
         return;
     }
     const uint32_t n = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
@@ -617,7 +638,7 @@ __global__ void __launch_bounds__(1024) k_composite_train_fwd_bwd_mse(
     }
     const bool marched = live && num_steps != 0 && offset + num_steps < M;
     // ---- forward
-    CompCarry k = {1.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
+    CompCarry<C> k;
     if (marched) {
         for (uint32_t s0 = 0; s0 < num_steps; s0 += 64) {
             const uint32_t s = s0 + lane;
@@ -625,38 +646,40 @@ __global__ void __launch_bounds__(1024) k_composite_train_fwd_bwd_mse(
             const size_t p = (size_t)offset + (active ? s : 0);
             const float sigma = sigmas[p];
             const float2 dl = reinterpret_cast<const float2*>(deltas)[p];
-            const float c0 = rgbs[p * 3], c1 = rgbs[p * 3 + 1], c2 = rgbs[p * 3 + 2];
-            float w, T_post, r_i, g_i, b_i, ws_i;
-            comp_chunk(active, sigma, dl.x, dl.y, c0, c1, c2, lane, k, w, T_post, r_i, g_i, b_i, ws_i);
+            float c[C];
+            FOR_CH(q, c[q] = rgbs[p * C + q]);
+            float w, T_post, c_i[C], ws_i;
+            comp_chunk<C>(active, sigma, dl.x, dl.y, c, lane, k, w, T_post, c_i, ws_i);
         }
     }
-    float o0 = 0.0f, o1 = 0.0f, o2 = 0.0f;
+    float o[C];
+    FOR_CH(q, o[q] = 0.0f);
     if (live) {
         if (marched) {
             const float rest = 1.0f - k.ws;
-            o0 = __fadd_rn(k.r, __fmul_rn(rest, mse.bg.at(index, 0)));
-            o1 = __fadd_rn(k.g, __fmul_rn(rest, mse.bg.at(index, 1)));
-            o2 = __fadd_rn(k.b, __fmul_rn(rest, mse.bg.at(index, 2)));
+            FOR_CH(q, o[q] = __fadd_rn(k.c[q], __fmul_rn(rest, mse.bg.at(index, q))));
         } else {
-            o0 = mse.bg.at(index, 0); o1 = mse.bg.at(index, 1); o2 = mse.bg.at(index, 2);
+            FOR_CH(q, o[q] = mse.bg.at(index, q));
         }
         if (lane == 0) {
             weights_sum[index] = marched ? k.ws : 0.0f;
-            image[(size_t)index * 3] = marched ? k.r : 0.0f;
-            image[(size_t)index * 3 + 1] = marched ? k.g : 0.0f;
-            image[(size_t)index * 3 + 2] = marched ? k.b : 0.0f;
-            out_image[(size_t)index * 3] = o0; out_image[(size_t)index * 3 + 1] = o1; out_image[(size_t)index * 3 + 2] = o2;
+            FOR_CH(q, image[(size_t)index * C + q] = marched ? k.c[q] : 0.0f);
+            FOR_CH(q, out_image[(size_t)index * C + q] = o[q]);
         }
     }
     // ---- loss value (every ray contributes, marched or not)
     if (mse.loss) {
         __shared__ float s_err[16];
         float e = 0.0f;
-        if (live && lane < 3) {
-            const float d = (lane == 0 ? o0 : lane == 1 ? o1 : o2) - mse.target[(size_t)index * 3 + lane];
+        if (live && lane < C) {
+            float ol;                                             // o[lane]
+            if constexpr (C == 1) ol = o[0];
+            else if constexpr (C == 2) ol = lane == 0 ? o[0] : o[1];
+            else ol = lane == 0 ? o[0] : lane == 1 ? o[1] : o[2];
+            const float d = ol - mse.target[(size_t)index * C + lane];
             e = d * d;
         }
-        e += dpp_take<0x102>(0.0f, e);                        // lanes 0..2 -> lane 0 (row_shl 2, 1)
+        e += dpp_take<0x102>(0.0f, e);                        // lanes 0..2 -> lane 0 (row_shl 2, 1); lanes >= C hold 0
         e += dpp_take<0x101>(0.0f, e);
         if (lane == 0) s_err[threadIdx.x >> 6] = e;
         __syncthreads();
@@ -670,32 +693,32 @@ __global__ void __launch_bounds__(1024) k_composite_train_fwd_bwd_mse(
     if (!marched) {
         if (live && num_steps != 0 && offset < M) {          // a dropped ray's reservation, clipped to the buffer
             for (size_t i = (size_t)offset + lane; i < (size_t)M; i += 64) grad_sigmas[i] = 0.0f;
-            for (size_t i = (size_t)offset * 3 + lane; i < (size_t)M * 3; i += 64) grad_rgbs[i] = 0.0f;
+            for (size_t i = (size_t)offset * C + lane; i < (size_t)M * C; i += 64) grad_rgbs[i] = 0.0f;
         }
         return;
     }
-    float gi0 = o0 - mse.target[(size_t)index * 3], gi1 = o1 - mse.target[(size_t)index * 3 + 1],
-          gi2 = o2 - mse.target[(size_t)index * 3 + 2];
+    float gi[C];
+    FOR_CH(q, gi[q] = o[q] - mse.target[(size_t)index * C + q]);
     const float gsc = mse.scale_mul ? mse.scale * mse.scale_mul[0] : mse.scale;
-    gi0 *= gsc; gi1 *= gsc; gi2 *= gsc;
-    const float gws = -(gi0 * mse.bg.at(index, 0) + gi1 * mse.bg.at(index, 1) + gi2 * mse.bg.at(index, 2));
-    const float r_final = k.r, g_final = k.g, b_final = k.b, ws_final = k.ws;
-    CompCarry kb = {1.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
+    FOR_CH(q, gi[q] *= gsc);
+    const float gws = -bg_dot<C>(gi, mse.bg, index);
+    float c_final[C];
+    FOR_CH(q, c_final[q] = k.c[q]);
+    const float ws_final = k.ws;
+    CompCarry<C> kb;
     for (uint32_t s0 = 0; s0 < num_steps; s0 += 64) {
         const uint32_t s = s0 + lane;
         const bool active = s < num_steps;
         const size_t p = (size_t)offset + (active ? s : 0);
         const float sigma = sigmas[p];
         const float2 dl = reinterpret_cast<const float2*>(deltas)[p];
-        const float c0 = rgbs[p * 3], c1 = rgbs[p * 3 + 1], c2 = rgbs[p * 3 + 2];
-        float w, T, r_i, g_i, b_i, ws_i;
-        comp_chunk(active, sigma, dl.x, dl.y, c0, c1, c2, lane, kb, w, T, r_i, g_i, b_i, ws_i);
+        float c[C];
+        FOR_CH(q, c[q] = rgbs[p * C + q]);
+        float w, T, c_i[C], ws_i;
+        comp_chunk<C>(active, sigma, dl.x, dl.y, c, lane, kb, w, T, c_i, ws_i);
         if (active) {
-            grad_rgbs[p * 3] = gi0 * w;
-            grad_rgbs[p * 3 + 1] = gi1 * w;
-            grad_rgbs[p * 3 + 2] = gi2 * w;
-            grad_sigmas[p] = dl.x * (gi0 * (T * c0 - (r_final - r_i)) + gi1 * (T * c1 - (g_final - g_i)) +
-                                     gi2 * (T * c2 - (b_final - b_i)) + gws * (T - (ws_final - ws_i)));
+            FOR_CH(q, grad_rgbs[p * C + q] = gi[q] * w);
+            grad_sigmas[p] = dl.x * (colour_terms<C>(gi, T, c, c_final, c_i) + gws * (T - (ws_final - ws_i)));
         }
     }
 }
@@ -974,6 +997,7 @@ __global__ void __launch_bounds__(256) k_march_rays_w(uint32_t n_alive, uint32_t
         zero_rows(xyzs, dirs, deltas, (uint32_t)base + got, (uint32_t)base + n_step, lane_id(), 64);
 }
 
+template <int C>
 __global__ void __launch_bounds__(256) k_composite_rays(uint32_t n_alive, uint32_t n_step,
                                                         const int32_t* __restrict__ rays_alive, float* rays_t,
                                                         const float* __restrict__ sigmas,
@@ -985,10 +1009,11 @@ __global__ void __launch_bounds__(256) k_composite_rays(uint32_t n_alive, uint32
     const int index = rays_alive[n];
     float t = rays_t[n];
     const float* s = sigmas + (size_t)n * n_step;
-    const float* c = rgbs + (size_t)n * n_step * 3;
+    const float* c = rgbs + (size_t)n * n_step * C;
     const float* dl = deltas + (size_t)n * n_step * 2;
     float weight_sum = weights_sum[index], d = depth[index];
-    float r = image[(size_t)index * 3], g = image[(size_t)index * 3 + 1], b = image[(size_t)index * 3 + 2];
+    float col[C];
+    FOR_CH(q, col[q] = image[(size_t)index * C + q]);
     uint32_t step = 0;
     while (step < n_step) {
         if (dl[0] == 0) break;
@@ -998,16 +1023,14 @@ __global__ void __launch_bounds__(256) k_composite_rays(uint32_t n_alive, uint32
         weight_sum += weight;
         t += dl[1];
         d = fmaf(weight, t, d);
-        r = fmaf(weight, c[0], r);
-        g = fmaf(weight, c[1], g);
-        b = fmaf(weight, c[2], b);
+        FOR_CH(q, col[q] = fmaf(weight, c[q], col[q]));
         if ((double)T < 1e-5) break;
-        s++; c += 3; dl += 2; step++;
+        s++; c += C; dl += 2; step++;
     }
     rays_t[n] = (step < n_step) ? -1.0f : t;
     weights_sum[index] = weight_sum;
     depth[index] = d;
-    image[(size_t)index * 3] = r; image[(size_t)index * 3 + 1] = g; image[(size_t)index * 3 + 2] = b;
+    FOR_CH(q, image[(size_t)index * C + q] = col[q]);
 }
 
 // Whole-frame inference compositing (enerf_composite_rays_frame): every ray's samples lie contiguously (the training
@@ -1017,6 +1040,7 @@ __global__ void __launch_bounds__(256) k_composite_rays(uint32_t n_alive, uint32
 // fp32 sum: a parallel scan would round differently), including its termination rule: the sample whose pre-sample
 // transmittance is already < 1e-5 is still accumulated, then the ray stops.  The background blend and the depth
 // normalisation of run_cuda (nerf/renderer.py:398-401) are the epilogue.
+template <int C>
 __global__ void __launch_bounds__(256) k_composite_rays_frame(const float* __restrict__ sigmas,
                                                               const float* __restrict__ rgbs,
                                                               const float* __restrict__ deltas,
@@ -1033,9 +1057,10 @@ __global__ void __launch_bounds__(256) k_composite_rays_frame(const float* __res
     if (offset + count >= M) count = 0;                         // the marcher's drop rule (cannot happen with M exact)
     const float near = nears[index], far = fars[index];
     float t = near;
-    float weight_sum = 0.0f, d = 0.0f, r = 0.0f, g = 0.0f, b = 0.0f;
+    float weight_sum = 0.0f, d = 0.0f, col[C];
+    FOR_CH(q, col[q] = 0.0f);
     const float* s = sigmas + offset;
-    const float* c = rgbs + (size_t)offset * 3;
+    const float* c = rgbs + (size_t)offset * C;
     const float* dl = deltas + (size_t)offset * 2;
     // samples are fetched eight at a time (one memory latency per eight samples instead of one per sample: the ray's
     // recurrence itself is a dozen flops) and consumed in order
@@ -1043,10 +1068,10 @@ __global__ void __launch_bounds__(256) k_composite_rays_frame(const float* __res
     uint32_t step = 0;
     bool done = false;
     while (step < count && !done) {
-        float ps[PF], pd0[PF], pd1[PF], pc0[PF], pc1[PF], pc2[PF];
+        float ps[PF], pd0[PF], pd1[PF], pc[C][PF];
         const uint32_t nb = count - step < (uint32_t)PF ? count - step : (uint32_t)PF;
         if (nb == (uint32_t)PF) {
-            // a whole group: 12 sixteen-byte loads (dword-aligned is all gfx950 asks of them) instead of 48 four-byte ones --
+            // a whole group: 6 + 2 C sixteen-byte loads (dword-aligned is all gfx950 asks of them) instead of 24 + 8 C four-byte ones --
             // every lane walks its own segment, so each load instruction is 64 separate line look-ups either way
             const float4 s0 = *reinterpret_cast<const float4*>(s), s1 = *reinterpret_cast<const float4*>(s + 4);
             ps[0] = s0.x; ps[1] = s0.y; ps[2] = s0.z; ps[3] = s0.w; ps[4] = s1.x; ps[5] = s1.y; ps[6] = s1.z; ps[7] = s1.w;
@@ -1055,21 +1080,23 @@ __global__ void __launch_bounds__(256) k_composite_rays_frame(const float* __res
                 const float4 v = *reinterpret_cast<const float4*>(dl + 4 * q);
                 pd0[2 * q] = v.x; pd1[2 * q] = v.y; pd0[2 * q + 1] = v.z; pd1[2 * q + 1] = v.w;
             }
-            float cc[24];
+            float cc[PF * C];
 #pragma unroll
-            for (int q = 0; q < 6; q++) {
+            for (int q = 0; q < 2 * C; q++) {
                 const float4 v = *reinterpret_cast<const float4*>(c + 4 * q);
                 cc[4 * q] = v.x; cc[4 * q + 1] = v.y; cc[4 * q + 2] = v.z; cc[4 * q + 3] = v.w;
             }
 #pragma unroll
-            for (int k = 0; k < PF; k++) { pc0[k] = cc[3 * k]; pc1[k] = cc[3 * k + 1]; pc2[k] = cc[3 * k + 2]; }
+            for (int k = 0; k < PF; k++) {
+                FOR_CH(q, pc[q][k] = cc[C * k + q]);
+            }
         } else {
 #pragma unroll
             for (int k = 0; k < PF; k++) {
                 const uint32_t kk = (uint32_t)k < nb ? (uint32_t)k : nb - 1;
                 ps[k] = s[kk];
                 pd0[k] = dl[kk * 2]; pd1[k] = dl[kk * 2 + 1];
-                pc0[k] = c[kk * 3]; pc1[k] = c[kk * 3 + 1]; pc2[k] = c[kk * 3 + 2];
+                FOR_CH(q, pc[q][k] = c[kk * C + q]);
             }
         }
 #pragma unroll
@@ -1081,21 +1108,17 @@ __global__ void __launch_bounds__(256) k_composite_rays_frame(const float* __res
                 weight_sum += weight;
                 t += pd1[k];
                 d = fmaf(weight, t, d);
-                r = fmaf(weight, pc0[k], r);
-                g = fmaf(weight, pc1[k], g);
-                b = fmaf(weight, pc2[k], b);
+                FOR_CH(q, col[q] = fmaf(weight, pc[q][k], col[q]));
                 step++;
                 if ((double)T < 1e-5) done = true;
             }
         }
-        s += nb; c += (size_t)nb * 3; dl += (size_t)nb * 2;
+        s += nb; c += (size_t)nb * C; dl += (size_t)nb * 2;
     }
     if (used) atomicAdd(used, step);
     weights_sum[index] = weight_sum;
     const float rest = 1.0f - weight_sum;
-    image[(size_t)index * 3] = r + rest * bg.at(index, 0);
-    image[(size_t)index * 3 + 1] = g + rest * bg.at(index, 1);
-    image[(size_t)index * 3 + 2] = b + rest * bg.at(index, 2);
+    FOR_CH(q, image[(size_t)index * C + q] = col[q] + rest * bg.at(index, q));
     depth[index] = fmaxf(d - near, 0.0f) / (far - near);
 }
 
@@ -1482,45 +1505,141 @@ int enerf_march_rays_train_write(const float* rays_o, const float* rays_d, const
     return 0;
 }
 
-int enerf_composite_rays_train_forward(const float* sigmas, const float* rgbs, const float* deltas,
-                                       const int32_t* rays, uint32_t M, uint32_t N, float* weights_sum, float* depth,
-                                       float* image, enerf_stream_t stream) {
+// ---- compositing: the kernels are instantiated per channel count (the colour net's output width, 1..3); the entry points
+// named as the reference's (three channels by construction there) forward to the _c forms with 3
+#define ENERF_COMP_DISPATCH(channels, ...)          \
+    switch (channels) {                             \
+        case 1: { constexpr int C = 1; __VA_ARGS__; } break; \
+        case 2: { constexpr int C = 2; __VA_ARGS__; } break; \
+        default: { constexpr int C = 3; __VA_ARGS__; } break; \
+    }
+#define ENERF_COMP_CHANNELS(what, channels) \
+    if ((channels) < 1u || (channels) > 3u) ENERF_BADARG(what ": %u colour channels (1..3 are served)", (unsigned)(channels))
+#define ENERF_COMP_BG(what, bg_color, bg_stride, channels) \
+    if ((bg_color) && (bg_stride) != 0 && (bg_stride) != (channels)) ENERF_BADARG(what ": bg_stride %u", (unsigned)(bg_stride))
+
+int enerf_composite_rays_train_forward_c(const float* sigmas, const float* rgbs, const float* deltas, const int32_t* rays,
+                                         uint32_t M, uint32_t N, float* weights_sum, float* depth, float* image,
+                                         uint32_t channels, enerf_stream_t stream) {
+    ENERF_COMP_CHANNELS("composite_rays_train_forward", channels);
     if (N == 0) return 0;
     hipStream_t s = (hipStream_t)stream;
     ProfScope prof(ENERF_K_COMPOSITE_FWD, s);
-    k_composite_train_fwd<<<div_up(N, 4), 256, 0, s>>>(sigmas, rgbs, deltas, rays, M, N, weights_sum, depth, image,
-                                                       Background{nullptr, 0, 0.0f}, nullptr);
+    ENERF_COMP_DISPATCH(channels, k_composite_train_fwd<C><<<div_up(N, 4), 256, 0, s>>>(
+        sigmas, rgbs, deltas, rays, M, N, weights_sum, depth, image, Background{nullptr, 0, 0.0f}, nullptr));
     ENERF_LAUNCH_CHECK("composite_rays_train_forward");
     return 0;
+}
+
+int enerf_composite_rays_train_forward_blend_c(const float* sigmas, const float* rgbs, const float* deltas,
+                                               const int32_t* rays, uint32_t M, uint32_t N, float* weights_sum,
+                                               float* depth, float* image, const float* bg_color, uint32_t bg_stride,
+                                               float bg_scalar, float* out_image, uint32_t channels,
+                                               enerf_stream_t stream) {
+    ENERF_COMP_CHANNELS("composite_rays_train_forward_blend", channels);
+    if (N == 0) return 0;
+    if (!out_image) ENERF_BADARG("composite_rays_train_forward_blend: out_image is required");
+    ENERF_COMP_BG("composite_rays_train_forward_blend", bg_color, bg_stride, channels);
+    hipStream_t s = (hipStream_t)stream;
+    ProfScope prof(ENERF_K_COMPOSITE_FWD, s);
+    ENERF_COMP_DISPATCH(channels, k_composite_train_fwd<C><<<div_up(N, 4), 256, 0, s>>>(
+        sigmas, rgbs, deltas, rays, M, N, weights_sum, depth, image, Background{bg_color, bg_stride, bg_scalar}, out_image));
+    ENERF_LAUNCH_CHECK("composite_rays_train_forward_blend");
+    return 0;
+}
+
+int enerf_composite_rays_train_backward_c(const float* grad_weights_sum, const float* grad_image, const float* sigmas,
+                                          const float* rgbs, const float* deltas, const int32_t* rays,
+                                          const float* weights_sum, const float* image, uint32_t M, uint32_t N,
+                                          float* grad_sigmas, float* grad_rgbs, uint32_t channels, enerf_stream_t stream) {
+    ENERF_COMP_CHANNELS("composite_rays_train_backward", channels);
+    if (N == 0) return 0;
+    hipStream_t s = (hipStream_t)stream;
+    ProfScope prof(ENERF_K_COMPOSITE_BWD, s);
+    ENERF_COMP_DISPATCH(channels, k_composite_train_bwd<false, C><<<div_up(N, 4), 256, 0, s>>>(
+        grad_weights_sum, grad_image, sigmas, rgbs, deltas, rays, weights_sum, image, M, N, grad_sigmas, grad_rgbs,
+        MseTail{}, div_up(N, 4)));
+    ENERF_LAUNCH_CHECK("composite_rays_train_backward");
+    return 0;
+}
+
+int enerf_composite_rays_train_backward_mse_c(const float* out_image, const float* target, float grad_scale,
+                                              const float* bg_color, uint32_t bg_stride, float bg_scalar,
+                                              const int32_t* counter, const float* sigmas, const float* rgbs,
+                                              const float* deltas, const int32_t* rays, const float* weights_sum,
+                                              const float* image, uint32_t M, uint32_t N, float* grad_sigmas,
+                                              float* grad_rgbs, float* loss, uint32_t channels, enerf_stream_t stream) {
+    ENERF_COMP_CHANNELS("composite_rays_train_backward_mse", channels);
+    hipStream_t s = (hipStream_t)stream;
+    if (N == 0) {
+        if (M) {
+            (void)hipMemsetAsync(grad_sigmas, 0, (size_t)M * 4, s);
+            (void)hipMemsetAsync(grad_rgbs, 0, (size_t)M * 4 * channels, s);
+        }
+        return 0;
+    }
+    if (!counter) ENERF_BADARG("composite_rays_train_backward_mse: counter is required");
+    ENERF_COMP_BG("composite_rays_train_backward_mse", bg_color, bg_stride, channels);
+    ProfScope prof(ENERF_K_COMPOSITE_BWD, s);
+    const uint32_t ray_blocks = div_up(N, 16);
+    ENERF_COMP_DISPATCH(channels, k_composite_train_bwd<true, C><<<ray_blocks + 16, 1024, 0, s>>>(
+        nullptr, nullptr, sigmas, rgbs, deltas, rays, weights_sum, image, M, N, grad_sigmas, grad_rgbs,
+        MseTail{out_image, target, grad_scale, Background{bg_color, bg_stride, bg_scalar}, counter, loss,
+                1.0f / ((float)C * (float)N), amp_state().scale},
+        ray_blocks));
+    ENERF_LAUNCH_CHECK("composite_rays_train_backward_mse");
+    return 0;
+}
+
+int enerf_composite_rays_train_fwd_bwd_mse_c(const float* sigmas, const float* rgbs, const float* deltas,
+                                             const int32_t* rays, uint32_t M, uint32_t N, float* weights_sum,
+                                             float* image, const float* bg_color, uint32_t bg_stride, float bg_scalar,
+                                             float* out_image, const float* target, float grad_scale,
+                                             const int32_t* counter, float* grad_sigmas, float* grad_rgbs, float* loss,
+                                             uint32_t channels, enerf_stream_t stream) {
+    ENERF_COMP_CHANNELS("composite_rays_train_fwd_bwd_mse", channels);
+    hipStream_t s = (hipStream_t)stream;
+    if (N == 0) {
+        if (M) {
+            (void)hipMemsetAsync(grad_sigmas, 0, (size_t)M * 4, s);
+            (void)hipMemsetAsync(grad_rgbs, 0, (size_t)M * 4 * channels, s);
+        }
+        return 0;
+    }
+    if (!counter || !target || !out_image || !weights_sum || !image)
+        ENERF_BADARG("composite_rays_train_fwd_bwd_mse: counter, target, out_image, weights_sum and image are required");
+    ENERF_COMP_BG("composite_rays_train_fwd_bwd_mse", bg_color, bg_stride, channels);
+    ProfScope prof(ENERF_K_COMPOSITE_BWD, s);
+    const uint32_t ray_blocks = div_up(N, 16);
+    ENERF_COMP_DISPATCH(channels, k_composite_train_fwd_bwd_mse<C><<<ray_blocks + 16, 1024, 0, s>>>(
+        sigmas, rgbs, deltas, rays, M, N, weights_sum, image, out_image, grad_sigmas, grad_rgbs,
+        MseTail{nullptr, target, grad_scale, Background{bg_color, bg_stride, bg_scalar}, counter, loss,
+                1.0f / ((float)C * (float)N), amp_state().scale},
+        ray_blocks));
+    ENERF_LAUNCH_CHECK("composite_rays_train_fwd_bwd_mse");
+    return 0;
+}
+
+int enerf_composite_rays_train_forward(const float* sigmas, const float* rgbs, const float* deltas,
+                                       const int32_t* rays, uint32_t M, uint32_t N, float* weights_sum, float* depth,
+                                       float* image, enerf_stream_t stream) {
+    return enerf_composite_rays_train_forward_c(sigmas, rgbs, deltas, rays, M, N, weights_sum, depth, image, 3, stream);
 }
 
 int enerf_composite_rays_train_forward_blend(const float* sigmas, const float* rgbs, const float* deltas,
                                              const int32_t* rays, uint32_t M, uint32_t N, float* weights_sum,
                                              float* depth, float* image, const float* bg_color, uint32_t bg_stride,
                                              float bg_scalar, float* out_image, enerf_stream_t stream) {
-    if (N == 0) return 0;
-    if (!out_image) ENERF_BADARG("composite_rays_train_forward_blend: out_image is required");
-    if (bg_color && bg_stride != 0 && bg_stride != 3) ENERF_BADARG("composite_rays_train_forward_blend: bg_stride %u", bg_stride);
-    hipStream_t s = (hipStream_t)stream;
-    ProfScope prof(ENERF_K_COMPOSITE_FWD, s);
-    k_composite_train_fwd<<<div_up(N, 4), 256, 0, s>>>(sigmas, rgbs, deltas, rays, M, N, weights_sum, depth, image,
-                                                       Background{bg_color, bg_stride, bg_scalar}, out_image);
-    ENERF_LAUNCH_CHECK("composite_rays_train_forward_blend");
-    return 0;
+    return enerf_composite_rays_train_forward_blend_c(sigmas, rgbs, deltas, rays, M, N, weights_sum, depth, image, bg_color,
+                                                      bg_stride, bg_scalar, out_image, 3, stream);
 }
 
 int enerf_composite_rays_train_backward(const float* grad_weights_sum, const float* grad_image, const float* sigmas,
                                         const float* rgbs, const float* deltas, const int32_t* rays,
                                         const float* weights_sum, const float* image, uint32_t M, uint32_t N,
                                         float* grad_sigmas, float* grad_rgbs, enerf_stream_t stream) {
-    if (N == 0) return 0;
-    hipStream_t s = (hipStream_t)stream;
-    ProfScope prof(ENERF_K_COMPOSITE_BWD, s);
-    k_composite_train_bwd<false><<<div_up(N, 4), 256, 0, s>>>(grad_weights_sum, grad_image, sigmas, rgbs, deltas, rays,
-                                                              weights_sum, image, M, N, grad_sigmas, grad_rgbs,
-                                                              MseTail{}, div_up(N, 4));
-    ENERF_LAUNCH_CHECK("composite_rays_train_backward");
-    return 0;
+    return enerf_composite_rays_train_backward_c(grad_weights_sum, grad_image, sigmas, rgbs, deltas, rays, weights_sum, image,
+                                                 M, N, grad_sigmas, grad_rgbs, 3, stream);
 }
 
 int enerf_composite_rays_train_backward_mse(const float* out_image, const float* target, float grad_scale,
@@ -1529,25 +1648,9 @@ int enerf_composite_rays_train_backward_mse(const float* out_image, const float*
                                             const float* deltas, const int32_t* rays, const float* weights_sum,
                                             const float* image, uint32_t M, uint32_t N, float* grad_sigmas,
                                             float* grad_rgbs, float* loss, enerf_stream_t stream) {
-    hipStream_t s = (hipStream_t)stream;
-    if (N == 0) {
-        if (M) {
-            (void)hipMemsetAsync(grad_sigmas, 0, (size_t)M * 4, s);
-            (void)hipMemsetAsync(grad_rgbs, 0, (size_t)M * 12, s);
-        }
-        return 0;
-    }
-    if (!counter) ENERF_BADARG("composite_rays_train_backward_mse: counter is required");
-    if (bg_color && bg_stride != 0 && bg_stride != 3) ENERF_BADARG("composite_rays_train_backward_mse: bg_stride %u", bg_stride);
-    ProfScope prof(ENERF_K_COMPOSITE_BWD, s);
-    const uint32_t ray_blocks = div_up(N, 16);
-    k_composite_train_bwd<true><<<ray_blocks + 16, 1024, 0, s>>>(
-        nullptr, nullptr, sigmas, rgbs, deltas, rays, weights_sum, image, M, N, grad_sigmas, grad_rgbs,
-        MseTail{out_image, target, grad_scale, Background{bg_color, bg_stride, bg_scalar}, counter, loss,
-                1.0f / (3.0f * (float)N), amp_state().scale},
-        ray_blocks);
-    ENERF_LAUNCH_CHECK("composite_rays_train_backward_mse");
-    return 0;
+    return enerf_composite_rays_train_backward_mse_c(out_image, target, grad_scale, bg_color, bg_stride, bg_scalar, counter,
+                                                     sigmas, rgbs, deltas, rays, weights_sum, image, M, N, grad_sigmas,
+                                                     grad_rgbs, loss, 3, stream);
 }
 
 int enerf_composite_rays_train_fwd_bwd_mse(const float* sigmas, const float* rgbs, const float* deltas,
@@ -1556,26 +1659,9 @@ int enerf_composite_rays_train_fwd_bwd_mse(const float* sigmas, const float* rgb
                                            float* out_image, const float* target, float grad_scale,
                                            const int32_t* counter, float* grad_sigmas, float* grad_rgbs, float* loss,
                                            enerf_stream_t stream) {
-    hipStream_t s = (hipStream_t)stream;
-    if (N == 0) {
-        if (M) {
-            (void)hipMemsetAsync(grad_sigmas, 0, (size_t)M * 4, s);
-            (void)hipMemsetAsync(grad_rgbs, 0, (size_t)M * 12, s);
-        }
-        return 0;
-    }
-    if (!counter || !target || !out_image || !weights_sum || !image)
-        ENERF_BADARG("composite_rays_train_fwd_bwd_mse: counter, target, out_image, weights_sum and image are required");
-    if (bg_color && bg_stride != 0 && bg_stride != 3) ENERF_BADARG("composite_rays_train_fwd_bwd_mse: bg_stride %u", bg_stride);
-    ProfScope prof(ENERF_K_COMPOSITE_BWD, s);
-    const uint32_t ray_blocks = div_up(N, 16);
-    k_composite_train_fwd_bwd_mse<<<ray_blocks + 16, 1024, 0, s>>>(
-        sigmas, rgbs, deltas, rays, M, N, weights_sum, image, out_image, grad_sigmas, grad_rgbs,
-        MseTail{nullptr, target, grad_scale, Background{bg_color, bg_stride, bg_scalar}, counter, loss,
-                1.0f / (3.0f * (float)N), amp_state().scale},
-        ray_blocks);
-    ENERF_LAUNCH_CHECK("composite_rays_train_fwd_bwd_mse");
-    return 0;
+    return enerf_composite_rays_train_fwd_bwd_mse_c(sigmas, rgbs, deltas, rays, M, N, weights_sum, image, bg_color, bg_stride,
+                                                    bg_scalar, out_image, target, grad_scale, counter, grad_sigmas,
+                                                    grad_rgbs, loss, 3, stream);
 }
 
 // tuning aid: workgroups of the background training march (0: one per CU)
@@ -1680,15 +1766,40 @@ int enerf_march_rays_ex(uint32_t n_alive, uint32_t n_step, const int32_t* rays_a
     return 0;
 }
 
-int enerf_composite_rays(uint32_t n_alive, uint32_t n_step, const int32_t* rays_alive, float* rays_t,
-                         const float* sigmas, const float* rgbs, const float* deltas, float* weights_sum, float* depth,
-                         float* image, enerf_stream_t stream) {
+int enerf_composite_rays_c(uint32_t n_alive, uint32_t n_step, const int32_t* rays_alive, float* rays_t,
+                           const float* sigmas, const float* rgbs, const float* deltas, float* weights_sum, float* depth,
+                           float* image, uint32_t channels, enerf_stream_t stream) {
+    ENERF_COMP_CHANNELS("composite_rays", channels);
     if (n_alive == 0) return 0;
     hipStream_t s = (hipStream_t)stream;
     ProfScope prof(ENERF_K_COMPOSITE_INFER, s);
-    k_composite_rays<<<div_up(n_alive, 256), 256, 0, s>>>(n_alive, n_step, rays_alive, rays_t, sigmas, rgbs, deltas,
-                                                          weights_sum, depth, image);
+    ENERF_COMP_DISPATCH(channels, k_composite_rays<C><<<div_up(n_alive, 256), 256, 0, s>>>(
+        n_alive, n_step, rays_alive, rays_t, sigmas, rgbs, deltas, weights_sum, depth, image));
     ENERF_LAUNCH_CHECK("composite_rays");
+    return 0;
+}
+
+int enerf_composite_rays(uint32_t n_alive, uint32_t n_step, const int32_t* rays_alive, float* rays_t,
+                         const float* sigmas, const float* rgbs, const float* deltas, float* weights_sum, float* depth,
+                         float* image, enerf_stream_t stream) {
+    return enerf_composite_rays_c(n_alive, n_step, rays_alive, rays_t, sigmas, rgbs, deltas, weights_sum, depth, image, 3,
+                                  stream);
+}
+
+int enerf_composite_rays_frame_c(const float* sigmas, const float* rgbs, const float* deltas, const int32_t* rays,
+                                 uint32_t N, uint32_t M, const float* nears, const float* fars, const float* bg_color,
+                                 uint32_t bg_stride, float bg_scalar, float* weights_sum, float* depth, float* image,
+                                 uint32_t* used_samples, uint32_t channels, enerf_stream_t stream) {
+    ENERF_COMP_CHANNELS("composite_rays_frame", channels);
+    if (N == 0) return 0;
+    // (the three-channel entry point has never checked its stride: only the new channel counts are held to 0 or C)
+    if (channels != 3u) ENERF_COMP_BG("composite_rays_frame", bg_color, bg_stride, channels);
+    hipStream_t s = (hipStream_t)stream;
+    ProfScope prof(ENERF_K_COMPOSITE_INFER, s);
+    const Background bg = {bg_color, bg_stride, bg_scalar};
+    ENERF_COMP_DISPATCH(channels, k_composite_rays_frame<C><<<div_up(N, 256), 256, 0, s>>>(
+        sigmas, rgbs, deltas, rays, N, M, nears, fars, bg, weights_sum, depth, image, used_samples));
+    ENERF_LAUNCH_CHECK("composite_rays_frame");
     return 0;
 }
 
@@ -1696,14 +1807,8 @@ int enerf_composite_rays_frame(const float* sigmas, const float* rgbs, const flo
                                uint32_t N, uint32_t M, const float* nears, const float* fars, const float* bg_color,
                                uint32_t bg_stride, float bg_scalar, float* weights_sum, float* depth, float* image,
                                uint32_t* used_samples, enerf_stream_t stream) {
-    if (N == 0) return 0;
-    hipStream_t s = (hipStream_t)stream;
-    ProfScope prof(ENERF_K_COMPOSITE_INFER, s);
-    const Background bg = {bg_color, bg_stride, bg_scalar};
-    k_composite_rays_frame<<<div_up(N, 256), 256, 0, s>>>(sigmas, rgbs, deltas, rays, N, M, nears, fars, bg, weights_sum,
-                                                          depth, image, used_samples);
-    ENERF_LAUNCH_CHECK("composite_rays_frame");
-    return 0;
+    return enerf_composite_rays_frame_c(sigmas, rgbs, deltas, rays, N, M, nears, fars, bg_color, bg_stride, bg_scalar,
+                                        weights_sum, depth, image, used_samples, 3, stream);
 }
 
 int enerf_compact_rays(uint32_t n_alive, int32_t* rays_alive, const int32_t* rays_alive_old, float* rays_t,

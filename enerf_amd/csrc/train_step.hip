@@ -255,20 +255,21 @@ int optimizer(Step& st, A* a, const char* who) {
 
 // compositing of one render of the event step, on its sigma / rgb rows and their gradients
 int blend(const enerf_event_step_args* a, const enerf_step_render& r, const float* sigma, const float* rgb) {
-    return enerf_composite_rays_train_forward_blend(sigma, rgb, r.deltas, r.rays, r.M, r.N, r.weights_sum, nullptr, r.image,
-                                                    a->bg_color, 0, 0.0f, r.out_image, a->stream);
+    return enerf_composite_rays_train_forward_blend_c(sigma, rgb, r.deltas, r.rays, r.M, r.N, r.weights_sum, nullptr, r.image,
+                                                      a->bg_color, 0, 0.0f, r.out_image, a->out_c, a->stream);
 }
 int blend_backward(const enerf_event_step_args* a, const enerf_step_render& r, const float* sigma, const float* rgb,
                    float* g_sigmas, float* g_rgbs) {
     // (its tail blocks zero the gradients of rows [counter, M): merged, the padding between the two renders' samples)
-    return enerf_composite_rays_train_backward_mse(r.g_image, nullptr, 1.0f, a->bg_color, 0, 0.0f, r.counter, sigma, rgb,
-                                                   r.deltas, r.rays, r.weights_sum, r.image, r.M, r.N, g_sigmas, g_rgbs, nullptr,
-                                                   a->stream);
+    return enerf_composite_rays_train_backward_mse_c(r.g_image, nullptr, 1.0f, a->bg_color, 0, 0.0f, r.counter, sigma, rgb,
+                                                     r.deltas, r.rays, r.weights_sum, r.image, r.M, r.N, g_sigmas, g_rgbs,
+                                                     nullptr, a->out_c, a->stream);
 }
 // the event loss and its gradient with respect to the two images
 int event_loss(const enerf_event_step_args* a) {
-    return enerf_event_loss_fwd_bwd(a->r[0].out_image, a->r[1].out_image, a->pols, a->r[0].N, a->use_luma, a->linlog, a->C_thres,
-                                    a->log_thres, a->upstream, a->r[0].g_image, a->r[1].g_image, a->delta, a->loss, a->stream);
+    return enerf_event_loss_fwd_bwd_c(a->r[0].out_image, a->r[1].out_image, a->pols, a->r[0].N, a->use_luma, a->linlog,
+                                      a->C_thres, a->log_thres, a->upstream, a->r[0].g_image, a->r[1].g_image, a->delta, a->loss,
+                                      a->out_c, a->stream);
 }
 
 }  // namespace
@@ -288,10 +289,10 @@ extern "C" int enerf_train_step_mse(enerf_train_step_args* a) {
     const uint32_t n_next = add_next(*a, next, 0, a->next_count_host);
     if (int rc = forward(st, a, b, true, 0)) return rc;
     // compositing forward + loss gradient + compositing backward
-    if (int rc = st.run(enerf_composite_rays_train_fwd_bwd_mse(a->sigma, a->rgb, a->deltas, a->rays, a->M, a->N, a->weights_sum,
-                                                               a->image, nullptr, 0, a->bg_scalar, a->out_image, a->target,
-                                                               a->grad_scale, a->counter, a->g_sigmas, a->g_rgbs, a->loss,
-                                                               a->stream)))
+    if (int rc = st.run(enerf_composite_rays_train_fwd_bwd_mse_c(a->sigma, a->rgb, a->deltas, a->rays, a->M, a->N, a->weights_sum,
+                                                                 a->image, nullptr, 0, a->bg_scalar, a->out_image, a->target,
+                                                                 a->grad_scale, a->counter, a->g_sigmas, a->g_rgbs, a->loss,
+                                                                 a->out_c, a->stream)))
         return rc;
     if (int rc = marches_begin(st, a, next, n_next, !dp)) return rc;
     const bool side = n_next && !st.counts;

@@ -150,22 +150,24 @@ def wants_no_event_term(opt):
 
 
 def event_loss_with_grads(image1, image2, pols, opt):
-    """-> (loss, delta, d loss / d image1, d loss / d image2).  On the device, fp32, C_thres != -1: one launch
-    (enerf_event_loss_fwd_bwd, csrc/event_pairs.hip) in place of the ~50 elementwise / reduction launches of
-    event_loss + autograd; anything else goes through those."""
+    """-> (loss, delta, d loss / d image1, d loss / d image2).  On the device, fp32, C_thres != -1, images of 1..3
+    channels (luma: three): one launch (enerf_event_loss_fwd_bwd_c, csrc/event_pairs.hip) in place of the ~50
+    elementwise / reduction launches of event_loss + autograd; anything else goes through those."""
+    C = image1.shape[-1]
     fused = (image1.is_cuda and opt.C_thres != -1 and image1.dtype == image2.dtype == pols.dtype == torch.float32
-             and image1.shape == image2.shape and image1.shape[-1] == 3 and pols.numel() * 3 == image1.numel())
+             and image1.shape == image2.shape and 1 <= C <= 3 and pols.numel() * C == image1.numel()
+             and (not opt.use_luma or C == 3))
     if fused:
         from . import _lib as L
         a, b, p = image1.detach().contiguous(), image2.detach().contiguous(), pols.contiguous()
         n = p.numel()
         g1, g2 = torch.empty_like(a), torch.empty_like(b)
-        delta = torch.empty(*a.shape[:-1], 1 if opt.use_luma else 3, dtype=torch.float32, device=a.device)
+        delta = torch.empty(*a.shape[:-1], 1 if opt.use_luma else C, dtype=torch.float32, device=a.device)
         loss = torch.empty((), dtype=torch.float32, device=a.device)
-        L.check(L.lib().enerf_event_loss_fwd_bwd(a.data_ptr(), b.data_ptr(), p.data_ptr(), n, int(bool(opt.use_luma)),
-                                                 int(bool(opt.linlog)), float(opt.C_thres), float(opt.log_thres), 1.0,
-                                                 g1.data_ptr(), g2.data_ptr(), delta.data_ptr(), loss.data_ptr(),
-                                                 L.stream_handle()), "event_loss_fwd_bwd")
+        L.check(L.lib().enerf_event_loss_fwd_bwd_c(a.data_ptr(), b.data_ptr(), p.data_ptr(), n, int(bool(opt.use_luma)),
+                                                   int(bool(opt.linlog)), float(opt.C_thres), float(opt.log_thres), 1.0,
+                                                   g1.data_ptr(), g2.data_ptr(), delta.data_ptr(), loss.data_ptr(), C,
+                                                   L.stream_handle()), "event_loss_fwd_bwd")
         return loss, delta, g1, g2
     a = image1.detach().requires_grad_(True)
     b = image2.detach().requires_grad_(True)
@@ -215,7 +217,7 @@ def train_step_events(model, data, opt, criterion=None, bg_color=None, bg_color_
 def train_step_events_manual(model, data, opt, after_forward=None, bg_color=None, defer_table=False,
                              after_mlp_backward=None, bg_color_no_evs=None):
     """The event-only step with the two renders driven without autograd (fused_render.render_train_raw /
-    backward_raw): only the loss itself -- a few elementwise ops on two [N,3] images -- goes through autograd, and its
+    backward_raw): only the loss itself -- a few elementwise ops on two [N,C] images -- goes through autograd, and its
     gradient is handed to the renders' closed backward.  Same values as train_step_events + loss.backward()
     (nerf/utils.py:482-546); leaves the gradients in p.grad and returns (loss, delta).  `after_forward()` is called
     once both forwards are queued, `after_mlp_backward()` once the second render's MLP backward kernels are."""
@@ -239,11 +241,12 @@ def train_step_events_manual(model, data, opt, after_forward=None, bg_color=None
         ctxs += [ctx3, ctx4]
     if after_forward is not None:
         after_forward()                                 # e.g. the next step's two marches on a side stream
-    loss, delta, g1, g2 = event_loss_with_grads(img1.view(*shape, 3), img2.view(*shape, 3), data["pols"], opt)
+    C = img1.shape[-1]
+    loss, delta, g1, g2 = event_loss_with_grads(img1.view(*shape, C), img2.view(*shape, C), data["pols"], opt)
     grads = [g1, g2]
     if no_ev:
-        a = img3.view(*nshape, 3).detach().requires_grad_(True)
-        b = img4.view(*nshape, 3).detach().requires_grad_(True)
+        a = img3.view(*nshape, C).detach().requires_grad_(True)
+        b = img4.view(*nshape, C).detach().requires_grad_(True)
         with torch.enable_grad():
             loss_no = no_event_loss(a, b, opt)
             g3, g4 = torch.autograd.grad(loss_no, [a, b])

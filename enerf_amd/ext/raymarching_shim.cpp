@@ -17,6 +17,14 @@ static const uint8_t* u8(const at::Tensor& t, const char* n) {
     return t.data_ptr<uint8_t>();
 }
 
+// colour channels of rgbs [.., C]: the compositing kernels serve 1..3 (the reference's prototypes are unchanged; its
+// kernels are three-channel)
+static uint32_t channels(const at::Tensor& rgbs) {
+    TORCH_CHECK(rgbs.dim() >= 2 && rgbs.size(-1) >= 1 && rgbs.size(-1) <= 3,
+                "rgbs must be [M,C] with 1..3 colour channels, got ", rgbs.sizes());
+    return (uint32_t)rgbs.size(-1);
+}
+
 void near_far_from_aabb(at::Tensor rays_o, at::Tensor rays_d, at::Tensor aabb, const uint32_t N, const float min_near,
                         at::Tensor nears, at::Tensor fars) {
     Launch l(rays_o);
@@ -62,9 +70,9 @@ void composite_rays_train_forward(at::Tensor sigmas, at::Tensor rgbs, at::Tensor
                                   const uint32_t M, const uint32_t N, at::Tensor weights_sum, at::Tensor depth,
                                   at::Tensor image) {
     Launch l(sigmas);
-    shim::ok(enerf_composite_rays_train_forward(f32(sigmas, "sigmas"), f32(rgbs, "rgbs"), f32(deltas, "deltas"),
-                                                i32(rays, "rays"), M, N, f32w(weights_sum, "weights_sum"),
-                                                f32w(depth, "depth"), f32w(image, "image"), l.stream),
+    shim::ok(enerf_composite_rays_train_forward_c(f32(sigmas, "sigmas"), f32(rgbs, "rgbs"), f32(deltas, "deltas"),
+                                                  i32(rays, "rays"), M, N, f32w(weights_sum, "weights_sum"),
+                                                  f32w(depth, "depth"), f32w(image, "image"), channels(rgbs), l.stream),
              "composite_rays_train_forward");
 }
 
@@ -73,11 +81,11 @@ void composite_rays_train_backward(at::Tensor grad_weights_sum, at::Tensor grad_
                                    at::Tensor image, const uint32_t M, const uint32_t N, at::Tensor grad_sigmas,
                                    at::Tensor grad_rgbs) {
     Launch l(sigmas);
-    shim::ok(enerf_composite_rays_train_backward(f32(grad_weights_sum, "grad_weights_sum"), f32(grad_image, "grad_image"),
-                                                 f32(sigmas, "sigmas"), f32(rgbs, "rgbs"), f32(deltas, "deltas"),
-                                                 i32(rays, "rays"), f32(weights_sum, "weights_sum"), f32(image, "image"),
-                                                 M, N, f32w(grad_sigmas, "grad_sigmas"), f32w(grad_rgbs, "grad_rgbs"),
-                                                 l.stream), "composite_rays_train_backward");
+    shim::ok(enerf_composite_rays_train_backward_c(f32(grad_weights_sum, "grad_weights_sum"), f32(grad_image, "grad_image"),
+                                                   f32(sigmas, "sigmas"), f32(rgbs, "rgbs"), f32(deltas, "deltas"),
+                                                   i32(rays, "rays"), f32(weights_sum, "weights_sum"), f32(image, "image"),
+                                                   M, N, f32w(grad_sigmas, "grad_sigmas"), f32w(grad_rgbs, "grad_rgbs"),
+                                                   channels(rgbs), l.stream), "composite_rays_train_backward");
 }
 
 void march_rays(const uint32_t n_alive, const uint32_t n_step, at::Tensor rays_alive, at::Tensor rays_t,
@@ -95,10 +103,10 @@ void composite_rays(const uint32_t n_alive, const uint32_t n_step, at::Tensor ra
                     at::Tensor sigmas, at::Tensor rgbs, at::Tensor deltas, at::Tensor weights_sum, at::Tensor depth,
                     at::Tensor image) {
     Launch l(sigmas);
-    shim::ok(enerf_composite_rays(n_alive, n_step, i32(rays_alive, "rays_alive"), f32w(rays_t, "rays_t"),
-                                  f32(sigmas, "sigmas"), f32(rgbs, "rgbs"), f32(deltas, "deltas"),
-                                  f32w(weights_sum, "weights_sum"), f32w(depth, "depth"), f32w(image, "image"), l.stream),
-             "composite_rays");
+    shim::ok(enerf_composite_rays_c(n_alive, n_step, i32(rays_alive, "rays_alive"), f32w(rays_t, "rays_t"),
+                                    f32(sigmas, "sigmas"), f32(rgbs, "rgbs"), f32(deltas, "deltas"),
+                                    f32w(weights_sum, "weights_sum"), f32w(depth, "depth"), f32w(image, "image"),
+                                    channels(rgbs), l.stream), "composite_rays");
 }
 
 void compact_rays(const uint32_t n_alive, at::Tensor rays_alive, at::Tensor rays_alive_old, at::Tensor rays_t,

@@ -26,18 +26,26 @@ FRAME_ENABLED = True
 CHUNK = 1 << 22          # samples per network launch in render_frame (activations of a chunk stay cache-sized)
 
 
+def _channels(model):
+    from .fused_render import channels
+    return channels(model)
+
+
 def frame_supported(model, rays_o, perturb, dt_gamma, bg_color):
     if not (FRAME_ENABLED and raymarching._DEVICE == "cuda" and rays_o.is_cuda and rays_o.dtype == torch.float32
             and not perturb and dt_gamma == 0 and model.bg_radius <= 0 and not torch.is_grad_enabled()):
         return False
+    C = _channels(model)
+    if not 1 <= C <= 3:                              # what the compositing kernels serve
+        return False
     if isinstance(bg_color, torch.Tensor):
         return (bg_color.is_cuda and bg_color.dtype == torch.float32 and bg_color.is_contiguous()
-                and bg_color.numel() in (1, 3, 3 * rays_o.shape[0]))
+                and bg_color.numel() in (1, C, C * rays_o.shape[0]))
     return True
 
 
 def render_frame(model, rays_o, rays_d, bg_color=1, max_steps=1024, trace=None):
-    """rays_o, rays_d [N,3] fp32 on the device -> (depth [N], image [N,3]).  `trace(dict)` (tests) receives every
+    """rays_o, rays_d [N,3] fp32 on the device -> (depth [N], image [N,C]).  `trace(dict)` (tests) receives every
     intermediate buffer."""
     N, dev = rays_o.shape[0], rays_o.device
     f32 = dict(dtype=torch.float32, device=dev)
@@ -52,7 +60,8 @@ def render_frame(model, rays_o, rays_d, bg_color=1, max_steps=1024, trace=None):
     M = total + 128 - total % 128
     xyzs, dirs, deltas = torch.empty(M, 3, **f32), torch.empty(M, 3, **f32), torch.empty(M, 2, **f32)
     _rb.march_rays_train_write(*geom, M, nears, fars, xyzs, dirs, deltas, rays, counter, 0, 1)
-    sigmas, rgbs = torch.empty(M, **f32), torch.empty(M, 3, **f32)
+    C = _channels(model)
+    sigmas, rgbs = torch.empty(M, **f32), torch.empty(M, C, **f32)
     scale = float(model.density_scale)
     into = getattr(model, "forward_into", None)
     for a in range(0, M, CHUNK):
@@ -64,7 +73,7 @@ def render_frame(model, rays_o, rays_d, bg_color=1, max_steps=1024, trace=None):
             rgbs[a:a + CHUNK] = c
     if scale != 1.0:
         sigmas *= scale
-    weights_sum, depth, image = torch.empty(N, **f32), torch.empty(N, **f32), torch.empty(N, 3, **f32)
+    weights_sum, depth, image = torch.empty(N, **f32), torch.empty(N, **f32), torch.empty(N, C, **f32)
     used = torch.zeros(1, dtype=torch.int32, device=dev) if trace is not None else None
     _rb.composite_rays_frame(sigmas, rgbs, deltas, rays, N, M, nears, fars, bg_color, weights_sum, depth, image, used)
     _rb.STATS["infer_samples"] += total
@@ -81,7 +90,7 @@ def render_rounds(model, rays_o, rays_d, bg_color=1, perturb=False, dt_gamma=0, 
     N, dev = rays_o.shape[0], rays_o.device
     nears, fars = raymarching.near_far_from_aabb(rays_o, rays_d, model.aabb_infer, model.min_near)
     acc = dict(dtype=torch.float32, device=dev)
-    weights_sum, depth, image = torch.zeros(N, **acc), torch.zeros(N, **acc), torch.zeros(N, 3, **acc)
+    weights_sum, depth, image = torch.zeros(N, **acc), torch.zeros(N, **acc), torch.zeros(N, _channels(model), **acc)
     alive = torch.zeros(2, N, dtype=torch.int32, device=dev)        # ping-pong: compaction reads one row, writes the other
     t_now = torch.zeros(2, N, **acc)
     torch.arange(N, out=alive[0])

@@ -21,17 +21,25 @@ from .backends import _raymarching as _rb
 ENABLED = True
 
 
+def channels(model):
+    """Colour channels of the model's renders: the colour net's output width (NeRFNetwork: out_dim_color; FFMLP: 3)."""
+    return int(getattr(model, "out_dim_color", 3))
+
+
 def supported(model, rays_o, rays_d, bg_color, dt_gamma):
+    C = channels(model)
+    if not 1 <= C <= 3:                           # the compositing kernels serve 1..3 channels
+        return False
     if not (ENABLED and fnet.ENABLED and model.training and model.cuda_ray and model.bg_radius <= 0
             and rays_o.is_cuda and rays_o.dtype == torch.float32 and rays_d.dtype == torch.float32
             and not torch.is_autocast_enabled() and not rays_o.requires_grad and not rays_d.requires_grad
             and _rm._DEVICE == "cuda" and torch.is_grad_enabled()):
         return False
     if isinstance(bg_color, torch.Tensor):
-        # the composite kernels take a scalar, one RGB or one RGB per ray, fp32 and dense; anything else the reference's
+        # the composite kernels take a scalar, one colour or one colour per ray, fp32 and dense; anything else the reference's
         # `image + (1 - ws)[:, None] * bg_color` would broadcast goes the op-by-op route
         if (bg_color.requires_grad or not bg_color.is_cuda or bg_color.dtype != torch.float32
-                or not bg_color.is_contiguous() or bg_color.numel() not in (1, 3, 3 * rays_o.view(-1, 3).shape[0])):
+                or not bg_color.is_contiguous() or bg_color.numel() not in (1, C, C * rays_o.view(-1, 3).shape[0])):
             return False
     probe = rays_o.view(-1, 3)
     return fnet.supported(model, probe, probe)
@@ -224,8 +232,9 @@ class _FusedRenderTrain(Function):
         sigmas = sigma if scale == 1.0 else sigma * scale
         weights_sum = torch.empty(N, dtype=torch.float32, device=dev)
         depth = torch.empty(N, dtype=torch.float32, device=dev)
-        image = torch.empty(N, 3, dtype=torch.float32, device=dev)
-        out_image = torch.empty(N, 3, dtype=torch.float32, device=dev)
+        C = rgb.shape[1]
+        image = torch.empty(N, C, dtype=torch.float32, device=dev)
+        out_image = torch.empty(N, C, dtype=torch.float32, device=dev)
         # composite + `image + (1 - weights_sum).unsqueeze(-1) * bg_color` in one launch
         _rb.composite_rays_train_forward_blend(sigmas, rgb, deltas, rays, M, N, weights_sum, depth, image, bg_color,
                                                out_image)
@@ -239,7 +248,7 @@ class _FusedRenderTrain(Function):
     @staticmethod
     def backward(ctx, _g_depth, g_image):
         sigmas, rgb, deltas, rays, weights_sum, image, bg_color, M, N, scale = ctx.rest
-        g_image = g_image.reshape(N, 3).float().contiguous()
+        g_image = g_image.reshape(N, rgb.shape[1]).float().contiguous()
         # out_image = image + (1 - weights_sum)[:, None] * bg  ->  d/d(weights_sum) = -(g . bg)
         g_ws = -(g_image * bg_color).sum(-1) if isinstance(bg_color, torch.Tensor) else -(g_image.sum(-1) * bg_color)
         g_ws = g_ws.reshape(N).contiguous()
@@ -392,7 +401,7 @@ def _finish_counted(model, pre):
 
 
 def render_train(model, rays_o, rays_d, bg_color, perturb, force_all_rays, dt_gamma, max_steps):
-    """-> depth [N], image [N,3] (+ the step counter bookkeeping of run_cuda)."""
+    """-> depth [N], image [N,C] (+ the step counter bookkeeping of run_cuda)."""
     pre = _take_or_march(model, rays_o, rays_d, perturb, dt_gamma, max_steps, force_all_rays=force_all_rays)
     return _FusedRenderTrain.apply(rays_o, model, bg_color, pre, *fnet.network_params(model))
 
@@ -485,7 +494,7 @@ SKIP_PADDING_ROWS = _os.environ.get("ENERF_SKIP_PADDING_ROWS", "1") != "0"      
 
 
 def render_train_raw(model, rays_o, rays_d, bg_color=1, perturb=True, dt_gamma=0, max_steps=1024, composite=True):
-    """Forward half of a training render without autograd: -> (image [N,3] blended with bg_color, ctx).  Feed the
+    """Forward half of a training render without autograd: -> (image [N,C] blended with bg_color, ctx).  Feed the
     gradient of whatever loss was computed on `image` to backward_raw(ctx, ...).  No depth.  composite=False leaves
     the compositing to backward_raw(target=...), which then runs it fused with its backward (the image is valid once
     that call is queued)."""
@@ -503,8 +512,9 @@ def render_train_raw(model, rays_o, rays_d, bg_color=1, perturb=True, dt_gamma=0
         scale = float(model.density_scale)
         sigmas = sigma if scale == 1.0 else sigma * scale
         weights_sum = torch.empty(N, dtype=torch.float32, device=dev)
-        image = torch.empty(N, 3, dtype=torch.float32, device=dev)
-        out_image = torch.empty(N, 3, dtype=torch.float32, device=dev)
+        C = rgb.shape[1]
+        image = torch.empty(N, C, dtype=torch.float32, device=dev)
+        out_image = torch.empty(N, C, dtype=torch.float32, device=dev)
         if isinstance(bg_color, torch.Tensor):
             bg_color = bg_color.detach().to(torch.float32).contiguous()
         if composite:
@@ -517,27 +527,28 @@ def render_train_raw(model, rays_o, rays_d, bg_color=1, perturb=True, dt_gamma=0
 
 def backward_raw(ctx, g_image=None, target=None, upstream=1.0, loss_out=None, raw=False, defer_table=0,
                  after_mlp=None):
-    """Backward half.  Either g_image = d loss / d image [N,3], or target [N,3] for loss = mean((image - target)^2) *
+    """Backward half.  Either g_image = d loss / d image [N,C], or target [N,C] for loss = mean((image - target)^2) *
     upstream (gradient and, with loss_out, value formed inside the composite backward).  -> the gradients of
     fused_network.network_params(model) (raw=True: (embedding gradient, flat dW), see fused_network.nerf_backward);
     the embedding gradient is None when it was added into an existing embeddings.grad."""
     N, M = ctx["N"], ctx["M"]
+    C = ctx["rgb"].shape[1]
     with torch.no_grad():
         g_sigmas = torch.empty_like(ctx["sigmas"])
         g_rgbs = torch.empty_like(ctx["rgb"])
         if target is not None and not ctx["composited"]:
             _rb.composite_rays_train_fwd_bwd_mse(ctx["sigmas"], ctx["rgb"], ctx["deltas"], ctx["rays"], M, N,
                                                  ctx["weights_sum"], ctx["image"], ctx["bg"], ctx["out_image"],
-                                                 target.contiguous().view(-1, 3), 2.0 * float(upstream) / (3 * N),
+                                                 target.contiguous().view(-1, C), 2.0 * float(upstream) / (C * N),
                                                  ctx["counter"], g_sigmas, g_rgbs, loss_out)
         elif target is not None:
-            _rb.composite_rays_train_backward_mse(ctx["out_image"], target.contiguous().view(-1, 3),
-                                                  2.0 * float(upstream) / (3 * N), ctx["bg"], ctx["counter"],
+            _rb.composite_rays_train_backward_mse(ctx["out_image"], target.contiguous().view(-1, C),
+                                                  2.0 * float(upstream) / (C * N), ctx["bg"], ctx["counter"],
                                                   ctx["sigmas"], ctx["rgb"], ctx["deltas"], ctx["rays"],
                                                   ctx["weights_sum"], ctx["image"], M, N, g_sigmas, g_rgbs, loss_out)
         else:
             assert ctx["composited"], "render_train_raw(composite=False) needs backward_raw(target=...)"
-            _rb.composite_rays_train_backward_mse(g_image.detach().to(torch.float32).contiguous().view(-1, 3), None,
+            _rb.composite_rays_train_backward_mse(g_image.detach().to(torch.float32).contiguous().view(-1, C), None,
                                                   1.0, ctx["bg"], ctx["counter"], ctx["sigmas"], ctx["rgb"],
                                                   ctx["deltas"], ctx["rays"], ctx["weights_sum"], ctx["image"], M, N,
                                                   g_sigmas, g_rgbs, None)
@@ -548,7 +559,7 @@ def backward_raw(ctx, g_image=None, target=None, upstream=1.0, loss_out=None, ra
 def train_step_mse(model, rays_o, rays_d, target, bg_color=1, perturb=True, dt_gamma=0, max_steps=1024, upstream=1.0,
                    after_forward=None, loss_out=None, raw=False, defer_table=False, after_mlp_backward=None):
     """Forward AND backward of a training render under loss = mean((image - target)^2) * upstream, without autograd:
-    -> (image [N,3], gradients of fused_network.network_params(model) in that order; the first is None when the
+    -> (image [N,C], gradients of fused_network.network_params(model) in that order; the first is None when the
     embedding gradient was added straight into the parameter's .grad).
 
     For loops whose loss is the reference's default (nerf/utils.py:628, MSE): the loss gradient and the blend's
@@ -649,7 +660,8 @@ def native_events_supported(model, data, loss_opt, opt):
     ro, rd = data["rays_evs_o1"], data["rays_evs_d1"]
     return (NATIVE_STEP and _budget(model) > 0 and float(model.density_scale) == 1.0 and hasattr(opt, "grid_table_plan")
             and loss_opt.event_only and loss_opt.C_thres != -1 and not loss_opt.render_kwargs
-            and int(getattr(loss_opt, "out_dim_color", 3)) == 3
+            and int(getattr(loss_opt, "out_dim_color", 3)) == channels(model)
+            and (not loss_opt.use_luma or channels(model) == 3)              # luma is a three-channel operation
             and data["images"].shape[0] == 1 and data["pols"].dtype == torch.float32 and data["pols"].is_cuda
             and data["rays_evs_o1"].shape == data["rays_evs_o2"].shape
             and data["pols"].numel() * 3 == data["rays_evs_o1"].numel()
@@ -721,11 +733,12 @@ def _native_ctx(model, N, M, Nn, Mn, dev):
     f32 = dict(dtype=torch.float32, device=dev)
     a = ctx["a"]
     t = _mlp_scratch(M, ctx["arch"], ctx["out_c"], lambda name, *shape: torch.empty(*shape, **f32))
-    t.update(weights_sum=torch.empty(N, **f32), image=torch.empty(N, 3, **f32), out_image=torch.empty(N, 3, **f32))
+    C = ctx["out_c"]
+    t.update(weights_sum=torch.empty(N, **f32), image=torch.empty(N, C, **f32), out_image=torch.empty(N, C, **f32))
     for name, buf in t.items():
         setattr(a, name, buf.data_ptr())
     a.N, a.M = N, M
-    a.bg_scalar, a.grad_scale = 1.0, 2.0 / (3 * N)
+    a.bg_scalar, a.grad_scale = 1.0, 2.0 / (C * N)
     ctx.update(t=t, stages=[_stage_set(Nn, Mn, dev) for _ in range(2)] if Nn else [], flip=0,
                out_image=t["out_image"])
     return ctx
@@ -755,14 +768,14 @@ def _native_events_ctx(model, N, Ms, Nn, Mn, luma, dev):
             n = flat.numel() // 2
             return flat[q * n:(q + 1) * n].view(*shape)
         t = _mlp_scratch(M, arch, out_c, fresh if tm is None else half)
-        t.update(weights_sum=torch.empty(N, **f32), image=torch.empty(N, 3, **f32), out_image=torch.empty(N, 3, **f32),
-                 g_image=torch.empty(N, 3, **f32))
+        t.update(weights_sum=torch.empty(N, **f32), image=torch.empty(N, out_c, **f32),
+                 out_image=torch.empty(N, out_c, **f32), g_image=torch.empty(N, out_c, **f32))
         ts.append(t)
         a.r[q].N, a.r[q].M = N, M
         for name, buf in t.items():
             setattr(a.r[q], name, buf.data_ptr())
         stages.append([_stage_set(Nn, Mn, dev, {k: v[q * Mn:(q + 1) * Mn] for k, v in pb.items()}) for pb in pairs])
-    delta = torch.empty(1, N, 1 if luma else 3, **f32)
+    delta = torch.empty(1, N, 1 if luma else out_c, **f32)
     a.delta = delta.data_ptr()
     ctx.update(t=ts, tm=tm, stages=stages, flip=[0, 0], delta=delta)
     return ctx
@@ -867,7 +880,7 @@ def train_step_native(model, rays_o, rays_d, target, opt, next_rays=None, side_s
                       dt_gamma=0, max_steps=1024, raw=False, defer_dp=False):
     """One closed-form RGB step (loss = mean((image - target)^2), white background) through enerf_train_step_mse:
     render of this batch (marched ahead of time when the previous step asked for it) + backward + the optimizer, and the
-    march of `next_rays` = (rays_o, rays_d) on `side_stream` behind the MLP backward.  -> blended image [N,3] (a buffer
+    march of `next_rays` = (rays_o, rays_d) on `side_stream` behind the MLP backward.  -> blended image [N,C] (a buffer
     that the next step of the same shape overwrites).  Gradients of the MLP weights are left in p.grad (views of one flat
     buffer, likewise reused), the table's dense gradient buffer comes back clean; the optimizer's step counts advance.
     raw=True (data parallel): the table's gradient is summed into the dense buffer `embeddings.grad` and NO optimizer
@@ -900,7 +913,7 @@ def train_step_native(model, rays_o, rays_d, target, opt, next_rays=None, side_s
             a = ctx["a"]
             _fill_step(ctx, a)
             _fill_samples(a, pre)
-            a.target = target.contiguous().view(-1, 3).data_ptr()
+            a.target = target.contiguous().view(-1, ctx["out_c"]).data_ptr()
             a.loss = None if loss_out is None else loss_out.data_ptr()
             # (bit 1: the sharded tail with an owner range set -- this rank's slice of the table stays as record lists)
             a.flags = _step_flags((3 if defer_dp else 1) if raw else 0)
@@ -962,7 +975,10 @@ def train_step_events_native(model, data, loss_opt, opt, next_data=None, side_st
     pairs = flat(data)
     N, dev = pairs[0][0].shape[0], pairs[0][0].device
     with torch.no_grad():
-        bg = torch.rand((1, 1, 3), device=dev) if bg_color is None else bg_color.detach().to(torch.float32).contiguous()
+        C = channels(model)
+        bg = torch.rand((1, 1, C), device=dev) if bg_color is None else bg_color.detach().to(torch.float32).contiguous()
+        if bg.numel() != C:
+            raise ValueError(f"train_step_events_native: one background colour of {C} values, got {bg.numel()}")
         pres, slots = [], []
         for ro, rd in pairs:
             pres.append(_take_or_march(model, ro, rd, perturb, dt_gamma, max_steps))

@@ -21,6 +21,17 @@ def _f32c(t):
     return t.float().contiguous()
 
 
+def _colour_channels(rgbs):
+    """C of rgbs [.., C].  The HIP kernels composite 1..3 channels; the CPU oracle backend is the reference's kernels,
+    three-channel by construction, so anything else must not reach it."""
+    C = int(rgbs.shape[-1]) if rgbs.dim() >= 2 else 0
+    if not 1 <= C <= 3:
+        raise ValueError(f"compositing takes rgbs [M,C] with 1..3 colour channels, got C = {C}")
+    if C != 3 and (rgbs.device.type != "cuda" or _DEVICE != "cuda"):
+        raise ValueError(f"compositing of C = {C} colour channels runs on the GPU only: the CPU oracle is three-channel")
+    return C
+
+
 # ---------------------------------------------------------------------------- utils
 class _near_far_from_aabb(Function):
     @staticmethod
@@ -155,7 +166,9 @@ class _composite_rays_train(Function):
     @staticmethod
     def forward(ctx, sigmas, rgbs, deltas, rays):
         """Front-to-back compositing of every ray's samples.   (raymarching.py:233-264)
-        sigmas [M], rgbs [M,3], deltas [M,2], rays [N,3] -> weights_sum [N], depth [N], image [N,3]"""
+        sigmas [M], rgbs [M,C], deltas [M,2], rays [N,3] -> weights_sum [N], depth [N], image [N,C]   (C = 1..3; the
+        reference's is 3)"""
+        C = _colour_channels(rgbs)
         sigmas = _f32c(sigmas)
         rgbs = _f32c(rgbs)
         deltas = _f32c(deltas)
@@ -163,7 +176,7 @@ class _composite_rays_train(Function):
         dev = sigmas.device
         weights_sum = torch.empty(N, dtype=torch.float32, device=dev)
         depth = torch.empty(N, dtype=torch.float32, device=dev)
-        image = torch.empty(N, 3, dtype=torch.float32, device=dev)
+        image = torch.empty(N, C, dtype=torch.float32, device=dev)
         _backend.composite_rays_train_forward(sigmas, rgbs, deltas, rays, M, N, weights_sum, depth, image)
         ctx.save_for_backward(sigmas, rgbs, deltas, rays, weights_sum, depth, image)
         ctx.dims = (M, N)
@@ -221,7 +234,8 @@ class _composite_rays(Function):
     @staticmethod
     def forward(ctx, n_alive, n_step, rays_alive, rays_t, sigmas, rgbs, deltas, weights_sum, depth, image):
         """In-place accumulation into weights_sum / depth / image; rays_t[n] = -1 marks a finished ray.
-        (raymarching.py:340-362)"""
+        (raymarching.py:340-362)   rgbs [.., C], image [N,C], C = 1..3"""
+        _colour_channels(rgbs)
         _backend.composite_rays(n_alive, n_step, rays_alive, rays_t, _f32c(sigmas), _f32c(rgbs), deltas, weights_sum,
                                 depth, image)
         return tuple()

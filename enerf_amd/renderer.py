@@ -121,7 +121,7 @@ class NeRFRenderer(nn.Module):
             depth, image = frame.render_frame(self, rays_o, rays_d, bg, max_steps)
         else:
             depth, image = frame.render_rounds(self, rays_o, rays_d, bg, perturb, dt_gamma, max_steps)
-        return {"depth": depth.view(*lead), "image": image.view(*lead, 3)}
+        return {"depth": depth.view(*lead), "image": image.view(*lead, int(getattr(self, "out_dim_color", 3)))}
 
     def _train_ops(self, rays_o, rays_d, bg, perturb, force_all_rays, dt_gamma, max_steps):
         """A training render through the four autograd Functions: slab test -> occupied samples of every

@@ -560,7 +560,7 @@ class TrainHarness:
         if loss is not None:
             return loss             # a view into the ring: overwritten one lap (64 steps) later -- clone to keep it
         with torch.no_grad():
-            return torch.nn.functional.mse_loss(image, target.view(-1, 3))
+            return torch.nn.functional.mse_loss(image, target.view(image.shape))
 
     def _reuse_cleared_grad(self, emb):
         """Only a buffer the last flush left clean may be added into: -> emb.grad when it is the buffer the last

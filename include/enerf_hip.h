@@ -65,8 +65,10 @@ const char* enerf_last_error(void);
  *     the rays of --negative_event_sampling).
  * 11: enerf_ema_update_multi added (the parameters' exponential moving average, Trainer's ema_decay).
  * 12: enerf_view_finish and enerf_view_minmax added (a rendered frame to display bytes: Trainer.test / test_gui, the GUI's
- *     running mean, scripts/render.py's min-max scaling). */
-#define ENERF_ABI_VERSION 12
+ *     running mean, scripts/render.py's min-max scaling).
+ * 13: the _c forms of the compositing entry points and of enerf_event_loss_fwd_bwd added (1..3 colour channels on the
+ *     marching route); both one-call steps honour out_c in their compositing and loss (target / g_image [N,out_c]). */
+#define ENERF_ABI_VERSION 13
 int enerf_abi_version(void);
 /* The library keeps grow-only scratch buffers per device (march chunk log, grid-backward record lists, ...).  Growing one
  * frees the old allocation; the counter returned here moves every time that happens.  A caller that captured library
@@ -248,6 +250,36 @@ int enerf_composite_rays_train_fwd_bwd_mse(const float* sigmas, const float* rgb
                                            const int32_t* counter, float* grad_sigmas, float* grad_rgbs, float* loss,
                                            enerf_stream_t stream);
 
+/* The five calls above for `channels` = 1, 2 or 3 colour channels (the colour net's output width; the reference's marching
+ * route is three-channel by construction): rgbs / grad_rgbs [M,channels], image / out_image / grad_image / target
+ * [N,channels], bg_color [channels] (bg_stride 0) or [N,channels] (bg_stride = channels); the MSE forms use
+ * grad_scale = 2 / (channels N) * upstream and report mean over N * channels values.  Everything else as documented above;
+ * the calls above are these with channels = 3.  channels outside 1..3: ENERF_E_BADARG. */
+int enerf_composite_rays_train_forward_c(const float* sigmas, const float* rgbs, const float* deltas, const int32_t* rays,
+                                         uint32_t M, uint32_t N, float* weights_sum, float* depth, float* image,
+                                         uint32_t channels, enerf_stream_t stream);
+int enerf_composite_rays_train_forward_blend_c(const float* sigmas, const float* rgbs, const float* deltas,
+                                               const int32_t* rays, uint32_t M, uint32_t N, float* weights_sum,
+                                               float* depth, float* image, const float* bg_color, uint32_t bg_stride,
+                                               float bg_scalar, float* out_image, uint32_t channels,
+                                               enerf_stream_t stream);
+int enerf_composite_rays_train_backward_c(const float* grad_weights_sum, const float* grad_image, const float* sigmas,
+                                          const float* rgbs, const float* deltas, const int32_t* rays,
+                                          const float* weights_sum, const float* image, uint32_t M, uint32_t N,
+                                          float* grad_sigmas, float* grad_rgbs, uint32_t channels, enerf_stream_t stream);
+int enerf_composite_rays_train_backward_mse_c(const float* out_image, const float* target, float grad_scale,
+                                              const float* bg_color, uint32_t bg_stride, float bg_scalar,
+                                              const int32_t* counter, const float* sigmas, const float* rgbs,
+                                              const float* deltas, const int32_t* rays, const float* weights_sum,
+                                              const float* image, uint32_t M, uint32_t N, float* grad_sigmas,
+                                              float* grad_rgbs, float* loss, uint32_t channels, enerf_stream_t stream);
+int enerf_composite_rays_train_fwd_bwd_mse_c(const float* sigmas, const float* rgbs, const float* deltas,
+                                             const int32_t* rays, uint32_t M, uint32_t N, float* weights_sum,
+                                             float* image, const float* bg_color, uint32_t bg_stride, float bg_scalar,
+                                             float* out_image, const float* target, float grad_scale,
+                                             const int32_t* counter, float* grad_sigmas, float* grad_rgbs, float* loss,
+                                             uint32_t channels, enerf_stream_t stream);
+
 /* raymarching.cu:807-813  march_rays(n_alive, n_step, rays_alive, rays_t, rays_o, rays_d, bound, dt_gamma,
  *                                    max_steps, C, H, grid, nears, fars, xyzs, dirs, deltas, perturb) */
 int enerf_march_rays(uint32_t n_alive, uint32_t n_step, const int32_t* rays_alive, const float* rays_t,
@@ -284,6 +316,17 @@ int enerf_composite_rays_frame(const float* sigmas, const float* rgbs, const flo
                                uint32_t N, uint32_t M, const float* nears, const float* fars, const float* bg_color,
                                uint32_t bg_stride, float bg_scalar, float* weights_sum, float* depth, float* image,
                                uint32_t* used_samples, enerf_stream_t stream);
+
+/* enerf_composite_rays / enerf_composite_rays_frame for `channels` = 1, 2 or 3 colour channels: rgbs [.., channels],
+ * image [N,channels], bg as in the training forms (one colour of `channels` values, or one per ray with
+ * bg_stride = channels).  channels outside 1..3: ENERF_E_BADARG. */
+int enerf_composite_rays_c(uint32_t n_alive, uint32_t n_step, const int32_t* rays_alive, float* rays_t,
+                           const float* sigmas, const float* rgbs, const float* deltas, float* weights_sum,
+                           float* depth, float* image, uint32_t channels, enerf_stream_t stream);
+int enerf_composite_rays_frame_c(const float* sigmas, const float* rgbs, const float* deltas, const int32_t* rays,
+                                 uint32_t N, uint32_t M, const float* nears, const float* fars, const float* bg_color,
+                                 uint32_t bg_stride, float bg_scalar, float* weights_sum, float* depth, float* image,
+                                 uint32_t* used_samples, uint32_t channels, enerf_stream_t stream);
 
 /* raymarching.cu:933-939  compact_rays(n_alive, rays_alive, rays_alive_old, rays_t, rays_t_old, alive_counter)
  * Order-preserving (stable) here; alive_counter[0] += number of survivors. */
@@ -653,6 +696,13 @@ int enerf_event_loss_fwd_bwd(const float* image1, const float* image2, const flo
                              uint32_t linlog, float C_thres, float log_thres, float upstream, float* grad_image1,
                              float* grad_image2, float* delta, float* loss, enerf_stream_t stream);
 
+/* The same for images of `channels` = 1, 2 or 3 channels: without luma, image1 / image2 / delta / grad_image1 /
+ * grad_image2 are [N,channels] and the mean runs over N * channels values.  Luma is a three-channel operation: use_luma
+ * with channels != 3 is ENERF_E_BADARG, as is channels outside 1..3. */
+int enerf_event_loss_fwd_bwd_c(const float* image1, const float* image2, const float* pols, uint32_t N, uint32_t use_luma,
+                               uint32_t linlog, float C_thres, float log_thres, float upstream, float* grad_image1,
+                               float* grad_image2, float* delta, float* loss, uint32_t channels, enerf_stream_t stream);
+
 /* One fused Adam update (torch.optim.Adam semantics, no weight decay / amsgrad) of a contiguous fp32 tensor:
  * reads p, g, m, v once and writes p, m, v (and g = 0 when zero_grad != 0).  `step` counts from 1. */
 int enerf_adam_step(float* p, float* g, float* m, float* v, size_t n, float lr, float beta1, float beta2, float eps,
@@ -698,7 +748,7 @@ typedef struct enerf_train_step_args {
     uint32_t N, M;
     const float *xyzs, *dirs, *deltas;
     const int32_t *rays, *counter;
-    const float* target;                /* [N,3] */
+    const float* target;                /* [N,out_c] */
     float bg_scalar, grad_scale;        /* d loss / d image = (out_image - target) * grad_scale */
     float* loss;                        /* device scalar the loss value is added into, or NULL */
     /* networks */
@@ -710,9 +760,9 @@ typedef struct enerf_train_step_args {
     const float* const* wseg_c;
     float* const* dwseg_s;              /* where the weight gradients are written (overwrite) */
     float* const* dwseg_c;
-    uint32_t nh_s, nh_c, w0_cols_c, out_c;
+    uint32_t nh_s, nh_c, w0_cols_c, out_c;   /* out_c: colour channels, 1..3 (the compositing's channel count) */
     /* scratch of the step, all fp32: feats [16,Mp,2], h32 [M,32], fb_s [nh_s,Mp,64], fb_c [nh_c,Mp,64], sigma [M],
-     * rgb [M,out_c], weights_sum [N], image [N,3], out_image [N,3], g_sigmas [M], g_rgbs [M,3], dx32 [M,32],
+     * rgb [M,out_c], weights_sum [N], image [N,out_c], out_image [N,out_c], g_sigmas [M], g_rgbs [M,out_c], dx32 [M,32],
      * dfeat [16,Mp,2] (Mp = M rounded up to 32) */
     float *feats, *h32, *fb_s, *fb_c, *sigma, *rgb, *weights_sum, *image, *out_image, *g_sigmas, *g_rgbs, *dx32, *dfeat;
     /* next batch's march (next_rays_o == NULL: none).  march_flags: enerf_march_rays_train_ex's zero_unwritten bits 0-3,
@@ -784,7 +834,7 @@ typedef struct enerf_step_render {
     uint32_t N, M;                      /* rays, sample rows budgeted (counter[0] real) */
     const float *xyzs, *dirs, *deltas;
     const int32_t *rays, *counter;
-    /* scratch, fp32 (shapes as in enerf_train_step_args; g_image [N,3] receives d loss / d out_image) */
+    /* scratch, fp32 (shapes as in enerf_train_step_args; g_image [N,out_c] receives d loss / d out_image) */
     float *feats, *h32, *fb_s, *fb_c, *sigma, *rgb, *weights_sum, *image, *out_image, *g_image, *g_sigmas, *g_rgbs, *dx32,
         *dfeat;
     /* the next step's march of this render's rays (next_rays_o == NULL: none) */
@@ -798,11 +848,11 @@ typedef struct enerf_event_step_args {
     int mlp_precision;
     enerf_stream_t stream, side_stream;
     enerf_step_render r[2];
-    const float* bg_color;              /* [3] device floats: one colour for both renders (nerf/utils.py:497) */
+    const float* bg_color;              /* [out_c] device floats: one colour for both renders (nerf/utils.py:497) */
     const float* pols;                  /* [N] */
     uint32_t use_luma, linlog;
     float C_thres, log_thres, upstream;
-    float *delta, *loss;                /* [N,1] (use_luma) or [N,3]; device scalar (written, may be NULL) */
+    float *delta, *loss;                /* [N,1] (use_luma, out_c = 3) or [N,out_c]; device scalar (written, may be NULL) */
     /* networks, march parameters, optimizer: as in enerf_train_step_args */
     const float* embeddings;
     const int32_t* offsets;
