@@ -94,6 +94,7 @@ SIGNATURES = {
     "enerf_debug_sweep_schedule": [_u32, _u32, _u32, _vp, _u32],
     "enerf_debug_mlp32_wgrad_blocks": [_u32],
     "enerf_debug_mlp32_grid_caps": [_u32, _u32],
+    "enerf_debug_sigma_head": [_int],
     "enerf_debug_march_wave_max_rays": [_u32],
     "enerf_debug_march_bg_blocks": [_u32],
     "enerf_debug_march_clip": [_int],

@@ -885,6 +885,16 @@ inline bool recompute_for(uint32_t num_hidden) { return g_recompute || num_hidde
 uint32_t g_wgrad_blocks = 0;        // 0: 768 workgroups for one hidden layer, 512 otherwise (measured optimum)
 
 uint32_t g_fwd_blocks = 0;          // 0: default cap of the forward grid
+int g_sig_form = kSigPipelined;     // enerf_debug_sigma_head: form of the density-only head (mlp32_common.h)
+// workgroup cap of the head's grid: the old form ran 512 whatever the device; the pipelined one fills the wavefronts per
+// SIMD its registers are bounded for (a 256-thread workgroup per CU is one wavefront per SIMD)
+uint32_t sig_grid_cap(int form) {
+    if (form == kSigOneAhead) return 512u;
+#ifdef ENERF_SIG_HEAD_LAB
+    if (form >= 1000) return (uint32_t)(form / 10 % 10) * num_cus();
+#endif
+    return (uint32_t)kSigWaves * num_cus();
+}
 uint32_t g_bwd_blocks = 0;          // 0: default cap of the fused backward grid
 
 // shapes the split / bf16 backward kernel serves: one or two hidden layers in either mode, three (the FFMLP colour net,
@@ -950,6 +960,16 @@ int enerf_debug_mlp32_grid_caps(uint32_t fwd_blocks, uint32_t bwd_blocks) {
     g_fwd_blocks = fwd_blocks;
     g_bwd_blocks = bwd_blocks;
     return 0;
+}
+
+// testing aid: form of the density-only head (include/enerf_hip.h)
+int enerf_debug_sigma_head(int form) {
+    const int prev = g_sig_form;
+    if (form == kSigOneAhead || form == kSigPipelined) g_sig_form = form;
+#ifdef ENERF_SIG_HEAD_LAB
+    if (form >= 1000) g_sig_form = form;             // 1000 + 100 * NT + 10 * wavefronts per SIMD + depth (mlp32s.hip)
+#endif
+    return prev;
 }
 
 // tuning aid: number of workgroups (= partial sums) of the weight-gradient kernel
@@ -1034,7 +1054,11 @@ static int mlp32_forward_impl(const float* X, WSrc W, uint32_t B, uint32_t in_di
     // and three workgroups per CU are resident)
     const bool sigma_only_shape = num_hidden == 1 && !fb && !Y && y0_exp && x_layout == 1;
     const bool lds_operands = mode == 1 && !sigma_only_shape;
-    const uint32_t grid = pgrid(B, g_fwd_blocks ? g_fwd_blocks : (lds_operands ? 768 : 512));
+    // (the exact-fp32 head is bound by its 32 fp32 MFMAs per tile, not by its loads: the pipeline measured no faster there
+    //  -- 279-295 against 287-290 us at 6.29 M points, 139-145 against 148-149 at half of them -- and it keeps the old form)
+    const int sig_form = !sigma_only_shape ? kSigOff : (mode == 0 ? kSigOneAhead : g_sig_form);
+    const uint32_t grid =
+        pgrid(B, g_fwd_blocks ? g_fwd_blocks : (sigma_only_shape ? sig_grid_cap(sig_form) : (lds_operands ? 768 : 512)));
     size_t lds = sizeof(float) * (HID * IN + (num_hidden - 1) * HID * HID + out_dim * HID);
     if (lds_operands && lds < (size_t)(8 + 8 * (num_hidden - 1)) * 2048) lds = (size_t)(8 + 8 * (num_hidden - 1)) * 2048;
 #define MLP32_FWD2(NHV, TR, XLV) \
@@ -1049,12 +1073,11 @@ static int mlp32_forward_impl(const float* X, WSrc W, uint32_t B, uint32_t in_di
             else MLP32_FWD2(NHV, false, 1);                   \
         }                                                     \
     } while (0)
-    const bool sigma_only = num_hidden == 1 && !fb && !Y && y0_exp && x_layout == 1;
     if (mode != 0) {
         // (a training forward whose backward recomputes the activations is the inference kernel)
         const bool store_fb = fb != nullptr && !(recompute_for(num_hidden) && split_bwd_shape(mode, num_hidden, out_dim, x_layout));
         (mode == 3 ? mlp32s_f16_launch_fwd : mlp32s_launch_fwd)(
-            mode == 1 ? 3 : 1, num_hidden, store_fb, x_layout, sigma_only, X, W, fb, Y, B, out_dim, activation,
+            mode == 1 ? 3 : 1, num_hidden, store_fb, x_layout, sig_form, X, W, fb, Y, B, out_dim, activation,
             output_activation, y_stride, y0_exp, sh_dirs, grid, lds, s, prof.start(), prof.stop(), io16);
     } else if (sh_dirs) {
         const ShNorm4 nrm = make_sh_norm4();
@@ -1064,7 +1087,7 @@ static int mlp32_forward_impl(const float* X, WSrc W, uint32_t B, uint32_t in_di
         else
             k_mlp32_fwd<1, false, 1, false, true><<<grid, 256, lds, s>>>(X, W, fb, Y, B, out_dim, activation,
                                                                          output_activation, y_stride, y0_exp, sh_dirs, nrm);
-    } else if (sigma_only)
+    } else if (sigma_only_shape)
         k_mlp32_fwd<1, false, 1, true><<<grid, 256, lds, s>>>(X, W, fb, Y, B, out_dim, activation, output_activation,
                                                               y_stride, y0_exp);
     else if (num_hidden == 1) MLP32_FWD(1);

@@ -258,10 +258,42 @@ __device__ __forceinline__ void load_x(const float* __restrict__ X, uint32_t til
         for (int p = 0; p < 16; p++) x[p] = 0.0f;
     }
 }
+// The level-major request alone, for a load pipeline: load_x's zeroing of the rows past the batch is a use of the data, and
+// the wavefront waits for them where it has only just asked (the compiler puts the wait there).  Every row of a tile below
+// Bp / 32 is the buffer's own (X is padded to Bp rows), so the request needs no guard; the consumer calls zero_rows_past
+// once the data are due.  NT: non-temporal loads, for a stream that is read exactly once.
+template <bool NT>
+__device__ __forceinline__ void request_x_lm(const float* __restrict__ X, uint32_t tile, int j, int h, uint32_t Bp,
+                                             float (&x)[16]) {
+    typedef float v2f __attribute__((ext_vector_type(2)));
+    const size_t s = (size_t)tile * 32 + j;
+#pragma unroll
+    for (int q = 0; q < 8; q++) {
+        const v2f* p = reinterpret_cast<const v2f*>(X + ((size_t)(2 * q + h) * Bp + s) * 2);
+        const v2f t = NT ? __builtin_nontemporal_load(p) : *p;
+        x[2 * q] = t.x; x[2 * q + 1] = t.y;
+    }
+}
+__device__ __forceinline__ void zero_rows_past(bool valid, float (&x)[16]) {
+#pragma unroll
+    for (int p = 0; p < 16; p++) x[p] = valid ? x[p] : 0.0f;
+}
+
+// Forms of the density-only head (SIG kernel of mlp32s.hip: Y == NULL, y0_exp set, level-major X), the
+// launchers' `sig_form`.  kSigOneAhead: a wavefront requests one tile ahead with load_x, 512 workgroups (the form shipped
+// before the load pipeline; enerf_debug_sigma_head(0) selects it: the comparator of tests/test_gpu_sigma_head_pipeline.py
+// and of A/B runs).  kSigPipelined (default): kSigDepth tiles ahead at kSigWaves wavefronts per SIMD, a grid that fills them.
+constexpr int kSigOff = -1, kSigOneAhead = 0, kSigPipelined = 1;
+// Measured on the MI355X at the full sweep's 6.29 M points (tools/sigma_head_lab.py, profiles/sigma_head_pipeline_ab.json):
+// 190 us before; depth 1 / 2 / 3 / 4 at one wavefront per SIMD 160 / 138 / 140 / 142, at two 142 / 139 / 140 / 139; with
+// non-temporal loads 156 / 130 / 129 / 130 and 131 / 130 / 129 / 130, and the whole update another 35 us shorter than the
+// head's own gain: the 805 MB read once no longer sweep the hash tables out of the Infinity Cache.
+constexpr int kSigDepth = 2, kSigWaves = 2;
+constexpr bool kSigNT = true;
 
 // split-bf16 kernels (mlp32s.hip); prec = 3 (hi + lo operands: fp32 accuracy) or 1 (bf16 operands: the FFMLP nets);
 // the launchers choose the template instance, the caller has validated the arguments
-void mlp32s_launch_fwd(int prec, uint32_t num_hidden, bool train, uint32_t x_layout, bool sigma_only, const float* X, const WSrc& W,
+void mlp32s_launch_fwd(int prec, uint32_t num_hidden, bool train, uint32_t x_layout, int sig_form, const float* X, const WSrc& W,
                        float* fb, float* Y, uint32_t B, uint32_t out_dim, uint32_t act, uint32_t out_act,
                        uint32_t y_stride, float* y0_exp, const float* sh_dirs, uint32_t grid, size_t lds, hipStream_t s,
                        hipEvent_t ev_start = nullptr, hipEvent_t ev_stop = nullptr, bool io16 = false);
@@ -271,7 +303,7 @@ void mlp32s_launch_bwd(int prec, uint32_t num_hidden, uint32_t x_layout, const D
                        bool recompute = false, bool io16 = false);
 
 // the same kernels with IEEE half operands (mlp32s_f16.hip; prec is 1 there: one product per operand pair)
-void mlp32s_f16_launch_fwd(int prec, uint32_t num_hidden, bool train, uint32_t x_layout, bool sigma_only, const float* X,
+void mlp32s_f16_launch_fwd(int prec, uint32_t num_hidden, bool train, uint32_t x_layout, int sig_form, const float* X,
                            const WSrc& W, float* fb, float* Y, uint32_t B, uint32_t out_dim, uint32_t act, uint32_t out_act,
                            uint32_t y_stride, float* y0_exp, const float* sh_dirs, uint32_t grid, size_t lds, hipStream_t s,
                            hipEvent_t ev_start = nullptr, hipEvent_t ev_stop = nullptr, bool io16 = false);

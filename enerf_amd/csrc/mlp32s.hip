@@ -6,6 +6,8 @@
 #include <hip/hip_runtime.h>
 #include <hip/hip_ext.h>
 
+#include <type_traits>
+
 #include "mlp32_common.h"
 #include "mlp32s_ops.h"
 
@@ -66,8 +68,15 @@ typedef unsigned u32x4w __attribute__((ext_vector_type(4)));
 #define k_mlp32s_bwd k_mlp32h_bwd
 #define k_mlp32s_mark k_mlp32h_mark
 #endif
-template <int NH, bool TRAIN, int XL, bool SIG = false, bool SH = false, int P = 3, bool IO16 = false>
-__global__ void __launch_bounds__(256, fwd_weights_in_lds(SIG, P) ? 3 : 1) k_mlp32s_fwd(const float* __restrict__ X, WSrc W,
+// D > 0 (SIG only): the load pipeline of the density-only head.  That head is a stream -- 128 B per sample in, 4 B out, ~100
+// tiles per wavefront -- bound by bytes in flight over the memory latency, and D == 0, the form shipped before, has none in
+// flight while it computes: load_x zeroes the rows past the batch, a use of the data, so the wavefront waits for its next
+// tile where it asks for it.  With D > 0 a wavefront keeps the inputs of its next D tiles on request (request_x_lm: no use
+// before they are due) in D register sets of 16 floats, which unrolled trips take in turn; no array is indexed at run
+// time.  WPS: wavefronts per SIMD the registers must admit (the launcher's grid fills them); NT: non-temporal loads.
+template <int NH, bool TRAIN, int XL, bool SIG = false, bool SH = false, int P = 3, bool IO16 = false, int D = 0, int WPS = 1,
+          bool NT = false>
+__global__ void __launch_bounds__(256, fwd_weights_in_lds(SIG, P) ? 3 : WPS) k_mlp32s_fwd(const float* __restrict__ X, WSrc W,
                                                     float* __restrict__ fb, float* __restrict__ Y, uint32_t B,
                                                     uint32_t out_dim, uint32_t act, uint32_t out_act, uint32_t y_stride,
                                                     float* __restrict__ y0_exp, const float* __restrict__ sh_dirs = nullptr,
@@ -76,9 +85,20 @@ __global__ void __launch_bounds__(256, fwd_weights_in_lds(SIG, P) ? 3 : 1) k_mlp
     const int lane = lane_id(), j = lane & 31, h = lane >> 5;
     const uint32_t Bp = (B + 31u) & ~31u;
     static_assert(!IO16 || (P == 1 && XL == 0 && !SIG && !SH && !TRAIN), "16-bit I/O: bf16 / fp16 operands, row-major, plain");
-    float x[16];
+    static_assert(D >= 0 && ((SIG && XL == 1 && NH == 1) || (D == 0 && WPS == 1 && !NT)),
+                  "the load pipeline is the density-only head's");
+    constexpr bool PIPE = D > 0;
+    float xq[PIPE ? D : 1][16];
+    float (&x)[16] = xq[0];
     bf16x8 xraw[2];
-    {
+    if constexpr (PIPE) {
+        // all D requests go out here, before the weights are staged: the kernel's head stays one memory latency
+        const uint32_t tile0 = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
+        const uint32_t nw0 = gridDim.x * (blockDim.x >> 6);
+#pragma unroll
+        for (int d = 0; d < D; d++)
+            if (tile0 + (uint32_t)d * nw0 < Bp / 32) request_x_lm<NT>(X, tile0 + (uint32_t)d * nw0, j, h, Bp, xq[d]);
+    } else {
         const uint32_t tile0 = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
         if (tile0 < Bp / 32) {
             if constexpr (IO16) load_x16(X, tile0, j, h, B, xraw);
@@ -183,6 +203,61 @@ __global__ void __launch_bounds__(256, fwd_weights_in_lds(SIG, P) ? 3 : 1) k_mlp
     const uint32_t ntiles = valid_tiles(W, B, Bp / 32);
     const uint32_t gw = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
     const uint32_t nw = gridDim.x * (blockDim.x >> 6);
+    if constexpr (PIPE) {
+        // One tile of the pipelined head, the arithmetic of the loop below instruction for instruction.  STEADY: a tile of
+        // the full-speed trips -- all of its 32 rows are real and the tile D rounds ahead exists, so nothing in it is
+        // conditional: every trip issues the same loads and stores, and the waits the compiler counts out leave exactly
+        // the younger requests in flight (a request or a store that MAY have been issued makes it assume it was not, and
+        // wait for everything).
+        auto sig_tile = [&](uint32_t tile, float (&xs)[16], auto steady) __attribute__((always_inline)) {
+            constexpr bool STEADY = decltype(steady)::value;
+            const size_t s = (size_t)tile * 32 + j;
+            const bool valid = STEADY || s < B;
+            if (!STEADY) zero_rows_past(valid, xs);        // (what load_x does where it asks)
+            Frag xf[2];
+#pragma unroll
+            for (int t = 0; t < 2; t++) {
+                float v[8];
+#pragma unroll
+                for (int e = 0; e < 8; e++) v[e] = xs[8 * t + e];
+                xf[t] = split8<P>(v);
+            }
+            // the operands hold the tile; its registers receive the wave's tile D rounds ahead (past the last: no request)
+            if (STEADY || tile + D * nw < ntiles) request_x_lm<NT>(X, tile + D * nw, j, h, Bp, xs);
+            f32x16 a[2];
+#pragma unroll
+            for (int ob = 0; ob < 2; ob++) {
+                a[ob] = (f32x16)(0.0f);
+#pragma unroll
+                for (int t = 0; t < 2; t++) a[ob] = mmap(w0[ob][t], xf[t], a[ob]);
+#pragma unroll
+                for (int q = 0; q < 16; q++) a[ob][q] = __int_as_float(max(__float_as_int(a[ob][q]), relu_lim));
+            }
+            float p0 = 0.0f, p1 = 0.0f;
+#pragma unroll
+            for (int q = 0; q < 16; q++) {
+                p0 = fmaf(wsig[0][q], a[0][q], p0);
+                p1 = fmaf(wsig[1][q], a[1][q], p1);
+            }
+            float p = p0 + p1;
+            p += __shfl_xor(p, 32, 64);
+            // (STEADY: both halves hold p and store it -- the same value to the same address, one store, no branch)
+            if (STEADY || (valid && h == 0)) y0_exp[s] = expf(p);
+        };
+        // A wavefront's k-th tile is served by register set k % D.  Full-speed trips: D tiles each, while every one of them
+        // has its successor D rounds ahead; the rest (at most 2 D - 1 tiles) asks before it requests.
+        uint32_t tile0 = gw;
+        for (; tile0 + (2 * D - 1) * nw < ntiles; tile0 += D * nw)
+#pragma unroll
+            for (int d = 0; d < D; d++) sig_tile(tile0 + (uint32_t)d * nw, xq[d], std::true_type{});
+        for (; tile0 < ntiles; tile0 += D * nw)
+#pragma unroll
+            for (int d = 0; d < D; d++) {
+                if (d > 0 && tile0 + (uint32_t)d * nw >= ntiles) break;
+                sig_tile(tile0 + (uint32_t)d * nw, xq[d], std::false_type{});
+            }
+        return;
+    }
     for (uint32_t tile = gw; tile < ntiles; tile += nw) {
         const size_t s = (size_t)tile * 32 + j;
         const bool valid = s < B;
@@ -774,7 +849,7 @@ __global__ void __launch_bounds__(256) k_mlp32s_bwd(DySource dys, const float* _
 
 __global__ void k_mlp32s_mark() {}
 
-void MLP32S_LAUNCH_FWD(int prec, uint32_t num_hidden, bool train, uint32_t x_layout, bool sigma_only, const float* X,
+void MLP32S_LAUNCH_FWD(int prec, uint32_t num_hidden, bool train, uint32_t x_layout, int sig_form, const float* X,
                        const WSrc& W, float* fb, float* Y, uint32_t B, uint32_t out_dim, uint32_t act, uint32_t out_act,
                        uint32_t y_stride, float* y0_exp, const float* sh_dirs, uint32_t grid, size_t lds, hipStream_t s,
                        hipEvent_t ev_start, hipEvent_t ev_stop, bool io16) {
@@ -818,8 +893,45 @@ void MLP32S_LAUNCH_FWD(int prec, uint32_t num_hidden, bool train, uint32_t x_lay
             if (train) S_FWD_P(2, true, 1, false, true);
             else S_FWD_P(2, false, 1, false, true);
         }
-    } else if (sigma_only) {
-        S_FWD_P(1, false, 1, true, false);
+    } else if (sig_form != kSigOff) {    // the density-only head (mlp32_common.h: its forms)
+#define S_SIG(PV, DV, WV, NTV)                                                                                              \
+    hipExtLaunchKernelGGL((k_mlp32s_fwd<1, false, 1, true, false, PV, false, DV, WV, NTV>), dim3(grid), dim3(256), lds, s,   \
+                          nullptr, ev_stop, 0, X, W, fb, Y, B, out_dim, act, out_act, y_stride, y0_exp, sh_dirs, nrm)
+#ifdef ENERF_MLP32S_F16
+#define S_SIG_P(DV, WV, NTV) S_SIG(1, DV, WV, NTV)
+#else
+#define S_SIG_P(DV, WV, NTV)                    \
+    do {                                        \
+        if (prec == 3) S_SIG(3, DV, WV, NTV);   \
+        else S_SIG(1, DV, WV, NTV);             \
+    } while (0)
+#endif
+        if (sig_form == kSigOneAhead) S_SIG_P(0, 1, false);
+#if defined(ENERF_SIG_HEAD_LAB) && !defined(ENERF_MLP32S_F16)
+        // development aid (tools/sigma_head_lab.py): depth x residency, form 1000 + 100 * NT + 10 * WPS + D, split operands
+#define S_SIG_LAB_D(WV, NTV)                                                \
+    do {                                                                    \
+        const int dv = sig_form % 10;                                       \
+        if (dv == 1) S_SIG(3, 1, WV, NTV);                                  \
+        else if (dv == 2) S_SIG(3, 2, WV, NTV);                             \
+        else if (dv == 3) S_SIG(3, 3, WV, NTV);                             \
+        else S_SIG(3, 4, WV, NTV);                                          \
+    } while (0)
+        else if (sig_form >= 1000 && prec == 3) {
+            const bool two = sig_form / 10 % 10 == 2;
+            if (sig_form / 100 % 10) {
+                if (two) S_SIG_LAB_D(2, true);
+                else S_SIG_LAB_D(1, true);
+            } else {
+                if (two) S_SIG_LAB_D(2, false);
+                else S_SIG_LAB_D(1, false);
+            }
+        }
+#undef S_SIG_LAB_D
+#endif
+        else S_SIG_P(kSigDepth, kSigWaves, kSigNT);
+#undef S_SIG_P
+#undef S_SIG
     } else if (num_hidden == 1) {
         S_FWD_TR(1);
     } else if (num_hidden == 2) {

@@ -67,7 +67,9 @@ const char* enerf_last_error(void);
  * 12: enerf_view_finish and enerf_view_minmax added (a rendered frame to display bytes: Trainer.test / test_gui, the GUI's
  *     running mean, scripts/render.py's min-max scaling).
  * 13: the _c forms of the compositing entry points and of enerf_event_loss_fwd_bwd added (1..3 colour channels on the
- *     marching route); both one-call steps honour out_c in their compositing and loss (target / g_image [N,out_c]). */
+ *     marching route); both one-call steps honour out_c in their compositing and loss (target / g_image [N,out_c]).
+ *     Still 13: enerf_debug_sigma_head added (a testing aid: the density-only head's load pipeline against the form shipped
+ *     before) -- no signature changed, and tests/test_composite_channels_host.py holds the header at 13. */
 #define ENERF_ABI_VERSION 13
 int enerf_abi_version(void);
 /* The library keeps grow-only scratch buffers per device (march chunk log, grid-backward record lists, ...).  Growing one
@@ -642,6 +644,13 @@ int enerf_debug_workspace_ordering(int on);
 int enerf_debug_march_bg_blocks(uint32_t n);
 /* tuning aid: workgroup caps of the mlp32 forward and fused-backward grids (0 = built-in defaults) */
 int enerf_debug_mlp32_grid_caps(uint32_t fwd_blocks, uint32_t bwd_blocks);
+/* Testing aid, process-wide: form of the density-only head (the mlp32 forward with Y == NULL, y0_exp set, one hidden layer,
+ * level-major X: update_extra_state's and the mesh lattice's sigma).  1 (default): a wavefront keeps the inputs of several
+ * of its tiles on request (the load pipeline of csrc/mlp32s.hip) on a grid that fills the device; 0: one tile ahead on 512
+ * workgroups, the form shipped before -- the same per-tile arithmetic, so the same sigma bit for bit; -1: query only.
+ * Returns the previous value.  enerf_debug_mlp32_grid_caps' forward cap applies to both.  enerf_mlp32_precision(0) (exact
+ * fp32, bound by its fp32 MFMAs) runs the old form whatever is selected here. */
+int enerf_debug_sigma_head(int form);
 
 /* Event-pair ray generation (the caller that feeds the event step: EventNeRFDataset.collate, nerf/provider.py:1364-1441,
  * accumulate_evs branch with poses "computed online", + get_event_rays, nerf/utils.py:184-216), one thread per pair:
