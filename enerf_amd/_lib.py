@@ -107,6 +107,7 @@ SIGNATURES = {
     "enerf_debug_march_thread_min_rays": [_u32],
     "enerf_event_loss_fwd_bwd": [_vp, _vp, _vp, _u32, _u32, _u32, _f32, _f32, _f32, _vp, _vp, _vp, _vp, _vp],
     "enerf_event_loss_fwd_bwd_c": [_vp, _vp, _vp, _u32, _u32, _u32, _f32, _f32, _f32, _vp, _vp, _vp, _vp, _u32, _vp],
+    "enerf_no_event_loss_fwd_bwd_c": [_vp, _vp, _u32, _u32, _f32, _f32, _vp, _vp, _vp, _u32, _vp],
     "enerf_event_pair_rays": [_vp, _vp, _vp, _vp, _u32, _vp, _vp, _u32, _u32, _vp, _vp, _vp, _vp, _u32, _f32, _f32, _f32,
                               _f32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
     "enerf_event_single_pair_rays": [_vp, _u32, _vp, _vp, _u32, _vp, _vp, _u32, _vp, _vp, _vp, _vp, _u32, _f32, _f32, _f32,

@@ -213,6 +213,168 @@ __global__ void __launch_bounds__(1024) k_event_loss(const float* __restrict__ i
     }
     if (threadIdx.x == 0 && loss) loss[0] = (float)(red[0] * (double)inv_count) * c.upstream;
 }
+
+// ---- sums of a 1024-thread workgroup for the two kernels below: across the 64 lanes of a wave in registers, then the 16
+// waves' partials through LDS; every thread leaves with the totals, added in wave order (the same order on every run).
+__device__ __forceinline__ double wave_sum(double v) {
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
+    return v;                                                        // (lane 0 holds the wave's sum)
+}
+template <int NS>
+__device__ __forceinline__ void block_sums_1024(double (&v)[NS], double (*part)[NS]) {   // part: LDS, [16][NS]
+    const uint32_t wave = threadIdx.x >> 6, lane = threadIdx.x & 63u;
+    for (int s = 0; s < NS; s++) {
+        const double w = wave_sum(v[s]);
+        if (lane == 0) part[wave][s] = w;
+    }
+    __syncthreads();
+    for (int s = 0; s < NS; s++) {
+        double t = 0.0;
+        for (int w = 0; w < 16; w++) t += part[w][s];
+        v[s] = t;
+    }
+}
+
+// ---- the normalised event loss (nerf/utils.py:521-528, C_thres == -1), forward and gradient in one launch -------------
+// Per channel k, over the N rays: u = d_k / (|d_k| + 1e-9), q = pol / (|pol| + 1e-9), loss = upstream * mean (u - q)^2.
+// Phase 1 forms delta (written out, un-normalised) and ONE reduction of Sdd_k = sum d_k^2, Spd_k = sum pol d_k and
+// Spp = sum pol^2 in double; the loss and sum_i r_i d_i follow from those in closed form (in double: the closed form of
+// the loss cancels).  With n = sqrt(Sdd), s = n + eps, sp = sqrt(Spp) + eps, c = 2 upstream / count the gradient is
+//   d loss / d d_j = A d_j - B pol_j,   B = c / (s sp),   A = c / s^2 * (eps / s + Spd / (sp n))
+// (1 - Sdd / (s n) written as eps / s: no cancellation), and A = c / s^2 when n == 0 -- torch's subgradient of the norm.
+// Phase 2: each thread re-reads the delta values it wrote itself and the images for dp/dl, and writes both gradients.
+template <int CH>
+__global__ void __launch_bounds__(1024) k_event_loss_norm(const float* __restrict__ img1, const float* __restrict__ img2,
+                                                          const float* __restrict__ pols, uint32_t N, EventLossCfg c,
+                                                          float* __restrict__ g1, float* __restrict__ g2,
+                                                          float* delta, float* __restrict__ loss) {
+    constexpr int NS = 2 * CH + 1;                                   // Sdd[CH], Spd[CH], Spp
+    __shared__ double part[16][NS];
+    const bool luma = CH == 3 && c.use_luma;
+    const int ch = luma ? 1 : CH;
+    double sums[NS];
+    for (int s = 0; s < NS; s++) sums[s] = 0.0;
+    for (uint32_t r = threadIdx.x; r < N; r += 1024u) {
+        const float* a = img1 + (size_t)r * CH;
+        const float* b = img2 + (size_t)r * CH;
+        const double pol = (double)pols[r];
+        sums[2 * CH] += pol * pol;
+        if (luma) {
+            float p1, d1, p2, d2;
+            ev_intensity(ev_luma(a), c, p1, d1);
+            // without lin-log the reference evaluates the second term on the FIRST luma (nerf/utils.py:500): delta = 0
+            ev_intensity(c.linlog ? ev_luma(b) : ev_luma(a), c, p2, d2);
+            const float dl = p2 - p1;
+            delta[r] = dl;
+            sums[0] += (double)dl * (double)dl;
+            sums[CH] += pol * (double)dl;
+        } else {
+            for (int k = 0; k < CH; k++) {
+                float p1, d1, p2, d2;
+                ev_intensity(a[k], c, p1, d1);
+                ev_intensity(b[k], c, p2, d2);
+                const float dl = p2 - p1;
+                delta[(size_t)r * CH + k] = dl;
+                sums[k] += (double)dl * (double)dl;
+                sums[CH + k] += pol * (double)dl;
+            }
+        }
+    }
+    block_sums_1024<NS>(sums, part);
+    const double eps = 1e-9, count = (double)N * (double)ch;
+    const double cc = 2.0 * (double)c.upstream / count;
+    const double spp = sums[2 * CH], sp = sqrt(spp) + eps;
+    double A[CH], B[CH], total = 0.0;
+    for (int k = 0; k < ch; k++) {
+        const double sdd = sums[k], spd = sums[CH + k];
+        const double n = sqrt(sdd), s = n + eps;
+        total += sdd / (s * s) - 2.0 * spd / (s * sp) + spp / (sp * sp);
+        B[k] = cc / (s * sp);
+        A[k] = n > 0.0 ? cc / (s * s) * (eps / s + spd / (sp * n)) : cc / (s * s);
+    }
+    if (threadIdx.x == 0 && loss) loss[0] = (float)((double)c.upstream * total / count);
+    for (uint32_t r = threadIdx.x; r < N; r += 1024u) {
+        const float* a = img1 + (size_t)r * CH;
+        const float* b = img2 + (size_t)r * CH;
+        const double pol = (double)pols[r];
+        float ga[3] = {0.f, 0.f, 0.f}, gb[3] = {0.f, 0.f, 0.f};
+        if (luma) {
+            float p1, d1, p2, d2;
+            ev_intensity(ev_luma(a), c, p1, d1);
+            ev_intensity(c.linlog ? ev_luma(b) : ev_luma(a), c, p2, d2);
+            const float gd = (float)(A[0] * (double)delta[r] - B[0] * pol);
+            const float w[3] = {0.299f, 0.587f, 0.114f};
+            for (int k = 0; k < 3; k++) {
+                if (c.linlog) { ga[k] = -gd * d1 * w[k]; gb[k] = gd * d2 * w[k]; }
+                else ga[k] = (gd * d2 - gd * d1) * w[k];
+            }
+        } else {
+            for (int k = 0; k < CH; k++) {
+                float p1, d1, p2, d2;
+                ev_intensity(a[k], c, p1, d1);
+                ev_intensity(b[k], c, p2, d2);
+                const float gd = (float)(A[k] * (double)delta[(size_t)r * CH + k] - B[k] * pol);
+                ga[k] = -gd * d1;
+                gb[k] = gd * d2;
+            }
+        }
+        for (int k = 0; k < CH; k++) {
+            g1[(size_t)r * CH + k] = ga[k];
+            g2[(size_t)r * CH + k] = gb[k];
+        }
+    }
+}
+
+// ---- the no-event hinge (nerf/utils.py:548-566), forward and gradient in one launch -------------------------------------
+// loss = upstream * mean relu(|p2 - p1| - C_no) over rays x channels (luma: rays), p always lin-log (c.linlog is set by the
+// entry point).  Gradient upstream / count * sign(p2 - p1) * [|p2 - p1| > C_no] * dp/dl: zero at the kink and at p2 == p1,
+// as torch's relu and abs give.  One workgroup, sum in double, fixed order.
+template <int CH>
+__global__ void __launch_bounds__(1024) k_no_event_loss(const float* __restrict__ img1, const float* __restrict__ img2,
+                                                        uint32_t N, EventLossCfg c, float c_no, float* __restrict__ g1,
+                                                        float* __restrict__ g2, float* __restrict__ loss) {
+    __shared__ double part[16][1];
+    const bool luma = CH == 3 && c.use_luma;
+    const double count = (double)N * (double)(luma ? 1 : CH);
+    const float scale = (float)((double)c.upstream / count);
+    double acc[1] = {0.0};
+    for (uint32_t r = threadIdx.x; r < N; r += 1024u) {
+        const float* a = img1 + (size_t)r * CH;
+        const float* b = img2 + (size_t)r * CH;
+        float ga[3] = {0.f, 0.f, 0.f}, gb[3] = {0.f, 0.f, 0.f};
+        if (luma) {
+            float p1, d1, p2, d2;
+            ev_intensity(ev_luma(a), c, p1, d1);
+            ev_intensity(ev_luma(b), c, p2, d2);
+            const float dl = p2 - p1, h = fabsf(dl) - c_no;
+            if (h > 0.0f) {
+                acc[0] += (double)h;
+                const float gd = dl > 0.0f ? scale : (dl < 0.0f ? -scale : 0.0f);
+                const float w[3] = {0.299f, 0.587f, 0.114f};
+                for (int k = 0; k < 3; k++) { ga[k] = -gd * d1 * w[k]; gb[k] = gd * d2 * w[k]; }
+            }
+        } else {
+            for (int k = 0; k < CH; k++) {
+                float p1, d1, p2, d2;
+                ev_intensity(a[k], c, p1, d1);
+                ev_intensity(b[k], c, p2, d2);
+                const float dl = p2 - p1, h = fabsf(dl) - c_no;
+                if (h > 0.0f) {
+                    acc[0] += (double)h;
+                    const float gd = dl > 0.0f ? scale : (dl < 0.0f ? -scale : 0.0f);
+                    ga[k] = -gd * d1;
+                    gb[k] = gd * d2;
+                }
+            }
+        }
+        for (int k = 0; k < CH; k++) {
+            g1[(size_t)r * CH + k] = ga[k];
+            g2[(size_t)r * CH + k] = gb[k];
+        }
+    }
+    block_sums_1024<1>(acc, part);
+    if (threadIdx.x == 0 && loss) loss[0] = (float)((double)c.upstream * acc[0] / count);
+}
 }  // namespace
 
 extern "C" int enerf_event_pair_rays(const float* events, const uint8_t* no_successor, const int64_t* num_successor,
@@ -290,8 +452,18 @@ extern "C" int enerf_event_loss_fwd_bwd_c(const float* image1, const float* imag
     if (N == 0) return 0;
     if (!image1 || !image2 || !pols || !grad_image1 || !grad_image2 || !delta)
         ENERF_BADARG("event_loss_fwd_bwd: images, pols, gradients and delta are required");
-    if (C_thres == -1.0f) ENERF_BADARG("event_loss_fwd_bwd: the normalised loss (C_thres == -1) is not fused");
     const EventLossCfg c = {use_luma, linlog, C_thres, log_thres, upstream};
+    const hipStream_t s = (hipStream_t)stream;
+    if (C_thres == -1.0f) {                                          // the normalised loss
+        if (channels == 1u)
+            k_event_loss_norm<1><<<1, 1024, 0, s>>>(image1, image2, pols, N, c, grad_image1, grad_image2, delta, loss);
+        else if (channels == 2u)
+            k_event_loss_norm<2><<<1, 1024, 0, s>>>(image1, image2, pols, N, c, grad_image1, grad_image2, delta, loss);
+        else
+            k_event_loss_norm<3><<<1, 1024, 0, s>>>(image1, image2, pols, N, c, grad_image1, grad_image2, delta, loss);
+        ENERF_LAUNCH_CHECK("event_loss_fwd_bwd(normalised)");
+        return 0;
+    }
     if (channels == 1u)
         k_event_loss<1><<<1, 1024, 0, (hipStream_t)stream>>>(image1, image2, pols, N, c, grad_image1, grad_image2, delta, loss);
     else if (channels == 2u)
@@ -299,5 +471,26 @@ extern "C" int enerf_event_loss_fwd_bwd_c(const float* image1, const float* imag
     else
         k_event_loss<3><<<1, 1024, 0, (hipStream_t)stream>>>(image1, image2, pols, N, c, grad_image1, grad_image2, delta, loss);
     ENERF_LAUNCH_CHECK("event_loss_fwd_bwd");
+    return 0;
+}
+
+extern "C" int enerf_no_event_loss_fwd_bwd_c(const float* image1, const float* image2, uint32_t N, uint32_t use_luma,
+                                             float C_no, float upstream, float* grad_image1, float* grad_image2,
+                                             float* loss, uint32_t channels, enerf_stream_t stream) {
+    if (channels < 1u || channels > 3u) ENERF_BADARG("no_event_loss_fwd_bwd: %u colour channels (1..3 are served)", channels);
+    if (use_luma && channels != 3u)
+        ENERF_BADARG("no_event_loss_fwd_bwd: luma is a three-channel operation (%u channels given)", channels);
+    if (N == 0) return 0;
+    if (!image1 || !image2 || !grad_image1 || !grad_image2)
+        ENERF_BADARG("no_event_loss_fwd_bwd: images and gradients are required");
+    const EventLossCfg c = {use_luma, 1u, 0.0f, 0.0f, upstream};     // lin-log whatever the event loss uses
+    const hipStream_t s = (hipStream_t)stream;
+    if (channels == 1u)
+        k_no_event_loss<1><<<1, 1024, 0, s>>>(image1, image2, N, c, C_no, grad_image1, grad_image2, loss);
+    else if (channels == 2u)
+        k_no_event_loss<2><<<1, 1024, 0, s>>>(image1, image2, N, c, C_no, grad_image1, grad_image2, loss);
+    else
+        k_no_event_loss<3><<<1, 1024, 0, s>>>(image1, image2, N, c, C_no, grad_image1, grad_image2, loss);
+    ENERF_LAUNCH_CHECK("no_event_loss_fwd_bwd");
     return 0;
 }

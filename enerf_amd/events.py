@@ -149,14 +149,24 @@ def wants_no_event_term(opt):
     return bool(getattr(opt, "negative_event_sampling", False)) and opt.epoch > opt.epoch_start_noEvLoss
 
 
+def _fused_images(image1, image2):
+    """Whether the loss kernels of csrc/event_pairs.hip take these two renders: on the device, fp32, the same shape,
+    1..3 channels."""
+    return (image1.is_cuda and image1.dtype == image2.dtype == torch.float32 and image1.shape == image2.shape
+            and 1 <= image1.shape[-1] <= 3)
+
+
 def event_loss_with_grads(image1, image2, pols, opt):
-    """-> (loss, delta, d loss / d image1, d loss / d image2).  On the device, fp32, C_thres != -1, images of 1..3
-    channels (luma: three): one launch (enerf_event_loss_fwd_bwd_c, csrc/event_pairs.hip) in place of the ~50
-    elementwise / reduction launches of event_loss + autograd; anything else goes through those."""
+    """-> (loss, delta, d loss / d image1, d loss / d image2).  On the device, fp32, images of 1..3 channels (luma:
+    three): one launch (enerf_event_loss_fwd_bwd_c, csrc/event_pairs.hip) in place of the ~50 elementwise / reduction
+    launches of event_loss + autograd; anything else goes through those.  The normalised loss (C_thres == -1) takes its
+    norms per batch entry: the kernel serves one entry, [1,N,C] images with [1,N] polarities (all the reference's collate
+    makes), and is handed the reference's weight -- 20, times 20 when frames are trained too -- as `upstream`."""
     C = image1.shape[-1]
-    fused = (image1.is_cuda and opt.C_thres != -1 and image1.dtype == image2.dtype == pols.dtype == torch.float32
-             and image1.shape == image2.shape and 1 <= C <= 3 and pols.numel() * C == image1.numel()
-             and (not opt.use_luma or C == 3))
+    normalised = opt.C_thres == -1
+    fused = (_fused_images(image1, image2) and pols.dtype == torch.float32 and pols.numel() * C == image1.numel()
+             and (not opt.use_luma or C == 3)
+             and (not normalised or (image1.dim() == 3 and image1.shape[0] == 1 and pols.dim() == 2)))
     if fused:
         from . import _lib as L
         a, b, p = image1.detach().contiguous(), image2.detach().contiguous(), pols.contiguous()
@@ -164,10 +174,11 @@ def event_loss_with_grads(image1, image2, pols, opt):
         g1, g2 = torch.empty_like(a), torch.empty_like(b)
         delta = torch.empty(*a.shape[:-1], 1 if opt.use_luma else C, dtype=torch.float32, device=a.device)
         loss = torch.empty((), dtype=torch.float32, device=a.device)
+        upstream = 1.0 if not normalised else (20.0 if opt.event_only else 400.0)
         L.check(L.lib().enerf_event_loss_fwd_bwd_c(a.data_ptr(), b.data_ptr(), p.data_ptr(), n, int(bool(opt.use_luma)),
-                                                   int(bool(opt.linlog)), float(opt.C_thres), float(opt.log_thres), 1.0,
-                                                   g1.data_ptr(), g2.data_ptr(), delta.data_ptr(), loss.data_ptr(), C,
-                                                   L.stream_handle()), "event_loss_fwd_bwd")
+                                                   int(bool(opt.linlog)), float(opt.C_thres), float(opt.log_thres),
+                                                   upstream, g1.data_ptr(), g2.data_ptr(), delta.data_ptr(),
+                                                   loss.data_ptr(), C, L.stream_handle()), "event_loss_fwd_bwd")
         return loss, delta, g1, g2
     a = image1.detach().requires_grad_(True)
     b = image2.detach().requires_grad_(True)
@@ -177,6 +188,28 @@ def event_loss_with_grads(image1, image2, pols, opt):
     g1 = torch.zeros_like(a) if g1 is None else g1
     g2 = torch.zeros_like(b) if g2 is None else g2
     return loss.detach(), delta.detach(), g1, g2
+
+
+def no_event_loss_with_grads(image1, image2, opt):
+    """-> (loss, d loss / d image1, d loss / d image2) of no_event_loss.  On the device, fp32, images of 1..3 channels
+    (luma: three): one launch (enerf_no_event_loss_fwd_bwd_c); anything else goes through no_event_loss + autograd."""
+    C = image1.shape[-1]
+    if _fused_images(image1, image2) and image1.numel() > 0 and (not opt.use_luma or C == 3):
+        from . import _lib as L
+        a, b = image1.detach().contiguous(), image2.detach().contiguous()
+        g1, g2 = torch.empty_like(a), torch.empty_like(b)
+        loss = torch.empty((), dtype=torch.float32, device=a.device)
+        cno = opt.C_thres if opt.C_thres > 0 else 0.25
+        L.check(L.lib().enerf_no_event_loss_fwd_bwd_c(a.data_ptr(), b.data_ptr(), a.numel() // C, int(bool(opt.use_luma)),
+                                                      float(cno), float(opt.w_no_ev), g1.data_ptr(), g2.data_ptr(),
+                                                      loss.data_ptr(), C, L.stream_handle()), "no_event_loss_fwd_bwd")
+        return loss, g1, g2
+    a = image1.detach().requires_grad_(True)
+    b = image2.detach().requires_grad_(True)
+    with torch.enable_grad():
+        loss = no_event_loss(a, b, opt)
+        g1, g2 = torch.autograd.grad(loss, [a, b])
+    return loss.detach(), g1, g2
 
 
 def train_step_events(model, data, opt, criterion=None, bg_color=None, bg_color_no_evs=None):
@@ -217,9 +250,9 @@ def train_step_events(model, data, opt, criterion=None, bg_color=None, bg_color_
 def train_step_events_manual(model, data, opt, after_forward=None, bg_color=None, defer_table=False,
                              after_mlp_backward=None, bg_color_no_evs=None):
     """The event-only step with the two renders driven without autograd (fused_render.render_train_raw /
-    backward_raw): only the loss itself -- a few elementwise ops on two [N,C] images -- goes through autograd, and its
-    gradient is handed to the renders' closed backward.  Same values as train_step_events + loss.backward()
-    (nerf/utils.py:482-546); leaves the gradients in p.grad and returns (loss, delta).  `after_forward()` is called
+    backward_raw): the losses and their image gradients come from event_loss_with_grads / no_event_loss_with_grads
+    (one launch each on the device), and the gradients are handed to the renders' closed backward.  Same values as
+    train_step_events + loss.backward() (nerf/utils.py:482-546); leaves the gradients in p.grad and returns (loss, delta).  `after_forward()` is called
     once both forwards are queued, `after_mlp_backward()` once the second render's MLP backward kernels are."""
     from . import fused_network as fnet
     from . import fused_render as fr
@@ -245,12 +278,8 @@ def train_step_events_manual(model, data, opt, after_forward=None, bg_color=None
     loss, delta, g1, g2 = event_loss_with_grads(img1.view(*shape, C), img2.view(*shape, C), data["pols"], opt)
     grads = [g1, g2]
     if no_ev:
-        a = img3.view(*nshape, C).detach().requires_grad_(True)
-        b = img4.view(*nshape, C).detach().requires_grad_(True)
-        with torch.enable_grad():
-            loss_no = no_event_loss(a, b, opt)
-            g3, g4 = torch.autograd.grad(loss_no, [a, b])
-        loss = loss + loss_no.detach()
+        loss_no, g3, g4 = no_event_loss_with_grads(img3.view(*nshape, C), img4.view(*nshape, C), opt)
+        loss = loss + loss_no
         grads += [g3, g4]
     params = fnet.network_params(model)
     emb = params[0]

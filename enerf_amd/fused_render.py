@@ -653,13 +653,13 @@ def native_step_supported(model, rays_o, rays_d, opt, data_parallel=False):
             and hasattr(opt, "grid_table_args") and supported(model, rays_o, rays_d, 1, 0))
 
 
-def native_events_supported(model, data, loss_opt, opt):
+def native_events_supported(model, data, loss_opt, opt, normalised=False):
     """What enerf_train_step_events serves: the steady state (a sample budget exists) of the event-only step with the
-    fused loss kernel (C_thres != -1, fp32, one background colour: a batch of one image), unit density scale, the fused
-    optimizer, default march parameters."""
+    fused loss kernel (fp32, one background colour: a batch of one image; the normalised loss, C_thres == -1, only where
+    the caller asks for it with `normalised`), unit density scale, the fused optimizer, default march parameters."""
     ro, rd = data["rays_evs_o1"], data["rays_evs_d1"]
     return (NATIVE_STEP and _budget(model) > 0 and float(model.density_scale) == 1.0 and hasattr(opt, "grid_table_plan")
-            and loss_opt.event_only and loss_opt.C_thres != -1 and not loss_opt.render_kwargs
+            and loss_opt.event_only and (loss_opt.C_thres != -1 or normalised) and not loss_opt.render_kwargs
             and int(getattr(loss_opt, "out_dim_color", 3)) == channels(model)
             and (not loss_opt.use_luma or channels(model) == 3)              # luma is a three-channel operation
             and data["images"].shape[0] == 1 and data["pols"].dtype == torch.float32 and data["pols"].is_cuda
@@ -996,7 +996,9 @@ def train_step_events_native(model, data, loss_opt, opt, next_data=None, side_st
         a.bg_color = bg.data_ptr()
         a.pols = data["pols"].contiguous().data_ptr()
         a.use_luma, a.linlog = int(bool(loss_opt.use_luma)), int(bool(loss_opt.linlog))
-        a.C_thres, a.log_thres, a.upstream = float(loss_opt.C_thres), float(loss_opt.log_thres), 1.0
+        # (the normalised loss carries the reference's weight of 20: event_only is a condition of this step)
+        a.C_thres, a.log_thres = float(loss_opt.C_thres), float(loss_opt.log_thres)
+        a.upstream = 20.0 if loss_opt.C_thres == -1 else 1.0
         a.loss = loss.data_ptr()
         for q, pre in enumerate(pres):
             _fill_samples(a.r[q], pre)

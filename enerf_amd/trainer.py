@@ -52,6 +52,7 @@ class TrainHarness:
         self.fuse_table_adam = True   # one GPU: the table gradient's tile sums feed Adam straight from LDS
         self.overlap_update = True    # update steps: the render's count pass is queued before the update's read-back
         self.native_step = True       # steady-state RGB steps on one GPU as ONE library call (enerf_train_step_mse)
+        self.native_normalised = False  # the one-call event step also at C_thres = -1 (the normalised loss): opt-in
         self._native_route_sig, self._native_route_dp, self._pending_sig = None, False, None
         self._params = [p for g in self.opt.param_groups for p in g["params"]]
         enc = getattr(model, "encoder", None)
@@ -930,7 +931,8 @@ class TrainHarness:
                     and self.prefetch_at == "mlp_backward" and hasattr(self.opt, "grid_table_plan")
                     and getattr(self.model, "graph_counter", None) is None):
                 from . import fused_render
-                if fused_render.native_events_supported(self.model, data, opt, self.opt):
+                if fused_render.native_events_supported(self.model, data, opt, self.opt,
+                                                        normalised=self.native_normalised):
                     return self._step_events_native(data, opt, next_data)
             side = None
             if next_data is not None and not opt.render_kwargs:

@@ -69,7 +69,9 @@ const char* enerf_last_error(void);
  * 13: the _c forms of the compositing entry points and of enerf_event_loss_fwd_bwd added (1..3 colour channels on the
  *     marching route); both one-call steps honour out_c in their compositing and loss (target / g_image [N,out_c]).
  *     Still 13: enerf_debug_sigma_head added (a testing aid: the density-only head's load pipeline against the form shipped
- *     before) -- no signature changed, and tests/test_composite_channels_host.py holds the header at 13. */
+ *     before) -- no signature changed, and tests/test_composite_channels_host.py holds the header at 13.
+ *     Still 13: enerf_no_event_loss_fwd_bwd_c added, and enerf_event_loss_fwd_bwd_c serves C_thres == -1 (the normalised
+ *     loss) where it answered ENERF_E_BADARG -- nothing existing changed meaning or layout. */
 #define ENERF_ABI_VERSION 13
 int enerf_abi_version(void);
 /* The library keeps grow-only scratch buffers per device (march chunk log, grid-backward record lists, ...).  Growing one
@@ -711,6 +713,20 @@ int enerf_event_loss_fwd_bwd(const float* image1, const float* image2, const flo
 int enerf_event_loss_fwd_bwd_c(const float* image1, const float* image2, const float* pols, uint32_t N, uint32_t use_luma,
                                uint32_t linlog, float C_thres, float log_thres, float upstream, float* grad_image1,
                                float* grad_image2, float* delta, float* loss, uint32_t channels, enerf_stream_t stream);
+/* C_thres == -1 selects the normalised loss (nerf/utils.py:521-528), also one launch: per channel k over the N rays,
+ * loss = upstream * mean_{rays,channels} (d_k / (|d_k|_2 + 1e-9) - pol / (|pol|_2 + 1e-9))^2, the N rays taken as ONE batch
+ * entry.  delta receives the un-normalised p2 - p1 as above.  Where |d_k|_2 == 0 the norm's gradient is taken as zero
+ * (torch's subgradient).  The reference weights this loss by 20, and by 20 again when frames are trained too
+ * (event_only = 0): that weight is not the kernel's business, the caller folds it into `upstream`. */
+
+/* The no-event term of --negative_event_sampling (nerf/utils.py:548-566) and its gradient, one launch:
+ * loss = upstream * mean(relu(|p2 - p1| - C_no)) over N * channels values (use_luma: over the N lumas; three channels
+ * only), p always the lin-log intensity.  grad_image1 / grad_image2 [N,channels] = upstream / count * sign(p2 - p1) *
+ * [|p2 - p1| > C_no] * dp/dl: zero at the kink and at p2 == p1.  loss [1] may be NULL.  Refusals as above; N == 0: no
+ * launch. */
+int enerf_no_event_loss_fwd_bwd_c(const float* image1, const float* image2, uint32_t N, uint32_t use_luma, float C_no,
+                                  float upstream, float* grad_image1, float* grad_image2, float* loss, uint32_t channels,
+                                  enerf_stream_t stream);
 
 /* One fused Adam update (torch.optim.Adam semantics, no weight decay / amsgrad) of a contiguous fp32 tensor:
  * reads p, g, m, v once and writes p, m, v (and g = 0 when zero_grad != 0).  `step` counts from 1. */
@@ -829,7 +845,8 @@ int enerf_debug_fold_reduce(int on);
 int enerf_debug_carry_count(int on);
 int enerf_debug_march_carry_blocks(uint32_t blocks);
 
-/* The event-only step (Trainer.train_step_events, nerf/utils.py:482-546, event_only = 1, C_thres != -1) the same way: TWO
+/* The event-only step (Trainer.train_step_events, nerf/utils.py:482-546, event_only = 1; C_thres == -1, the normalised
+ * loss, with the caller's weight of 20 in `upstream`) the same way: TWO
  * renders -- the event pairs' rays at the two poses -- blended with one background colour, the event loss on the two
  * images and its gradient (enerf_event_loss_fwd_bwd), both renders' backward, ONE optimizer pass; optionally the two
  * marches of the next step on `side_stream` behind the second render's MLP backward.  Calls, in order (what
