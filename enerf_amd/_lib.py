@@ -44,6 +44,8 @@ SIGNATURES = {
                                                _vp, _vp, _vp, _vp, _vp],
     "enerf_composite_rays_train_fwd_bwd_mse_c": [_vp, _vp, _vp, _vp, _u32, _u32, _vp, _vp, _vp, _u32, _f32, _vp, _vp, _f32,
                                                _vp, _vp, _vp, _vp, _u32, _vp],
+    "enerf_composite_rays_train_fwd_bwd_frames_c": [_vp, _vp, _vp, _vp, _u32, _u32, _vp, _vp, _vp, _u32, _f32, _vp, _vp, _u32,
+                                                    _f32, _vp, _vp, _vp, _vp, _vp, _vp, _u32, _vp],
     "enerf_composite_rays_train_backward": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _u32, _u32, _vp, _vp, _vp],
     "enerf_composite_rays_train_backward_c": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _u32, _u32, _vp, _vp, _u32, _vp],
     "enerf_composite_rays_frame": [_vp, _vp, _vp, _vp, _u32, _u32, _vp, _vp, _vp, _u32, _f32, _vp, _vp, _vp, _vp, _vp],

@@ -193,6 +193,21 @@ def composite_rays_train_fwd_bwd_mse(sigmas, rgbs, deltas, rays, M, N, weights_s
         "composite_rays_train_fwd_bwd_mse")
 
 
+def composite_rays_train_fwd_bwd_frames(sigmas, rgbs, deltas, rays, M, N, weights_sum, image, bg_color, out_image, pixels,
+                                        weight, counter, grad_sigmas, grad_rgbs, gt_out=None, err_out=None, loss=None):
+    """fwd_bwd_mse with the frame tail: pixels [N, C or C + 1] (alpha mixed on bg_color in the kernel), a weight on the
+    term, the per-ray error and the mixed ground truth on request (include/enerf_hip.h)."""
+    C = _channels(rgbs)
+    bg, stride, scalar = _background(bg_color, N, C)
+    opt = lambda t, name: None if t is None else _f32(t, name)
+    L.check(L.lib().enerf_composite_rays_train_fwd_bwd_frames_c(
+        _f32(sigmas, "sigmas"), _f32(rgbs, "rgbs"), _f32(deltas, "deltas"), _i32(rays, "rays"), int(M), int(N),
+        _f32(weights_sum, "weights_sum"), _f32(image, "image"), bg, stride, scalar, _f32(out_image, "out_image"),
+        _f32(pixels, "pixels"), int(pixels.shape[-1]), float(weight), opt(gt_out, "gt_out"), opt(err_out, "err_out"),
+        None if counter is None else _i32(counter, "counter"), _f32(grad_sigmas, "grad_sigmas"),
+        _f32(grad_rgbs, "grad_rgbs"), opt(loss, "loss"), C, L.stream_handle()), "composite_rays_train_fwd_bwd_frames")
+
+
 def composite_rays_train_forward(sigmas, rgbs, deltas, rays, M, N, weights_sum, depth, image):
     L.check(L.lib().enerf_composite_rays_train_forward_c(_f32(sigmas, "sigmas"), _f32(rgbs, "rgbs"),
                                                          _f32(deltas, "deltas"), _i32(rays, "rays"), int(M), int(N),

@@ -527,6 +527,45 @@ struct MseTail {
     const float* scale_mul; // optional (enerf_amp_begin): the gradient -- not the reported loss -- is multiplied by *scale_mul
 };
 
+// the frame form of the tail (Trainer.train_step, nerf/utils.py:595-604,634): the target is the frame's pixel, mixed on the
+// render's own background where it carries an alpha; the squared error is wanted per ray, and the term has a weight
+struct FrameTail {
+    const float* pixels;    // [N, pix_stride], pix_stride = C (finished colours) or C + 1 (colours, alpha)
+    uint32_t pix_stride;
+    float scale;            // 2 / (C N): d/d(out_image) of the unweighted term
+    float weight;           // the term's weight: on the loss (in loss_scale) and on the finished gradients
+    Background bg;
+    const int32_t* counter;
+    float* loss;            // optional: += loss_scale * sum_rays err (one atomic per workgroup), loss_scale = weight / N
+    float loss_scale;
+    const float* scale_mul; // as MseTail's
+    float* gt_out;          // optional [N,C]: the ground truth as formed here
+    float* err_out;         // optional [N]: sum_c (out_image - gt)^2 / C
+};
+template <typename Tail>
+struct is_frame_tail { static constexpr bool value = false; };
+template <>
+struct is_frame_tail<FrameTail> { static constexpr bool value = true; };
+
+// gt = pixels, or torch's `images[..., :C] * a + bg * (1 - a)` with every operation rounded on its own
+template <int C>
+__device__ __forceinline__ void frame_gt(const FrameTail& t, uint32_t ray, float (&gt)[C]) {
+    const float* p = t.pixels + (size_t)ray * t.pix_stride;
+    if (t.pix_stride == (uint32_t)C) {
+        FOR_CH(q, gt[q] = p[q]);
+    } else {
+        const float a = p[C];
+        const float rest = __fsub_rn(1.0f, a);
+        FOR_CH(q, gt[q] = __fadd_rn(__fmul_rn(p[q], a), __fmul_rn(t.bg.at(ray, q), rest)));
+    }
+}
+template <int C>
+__device__ __forceinline__ float sq_sum(const float (&d)[C]) {
+    if constexpr (C == 1) return d[0] * d[0];
+    else if constexpr (C == 2) return d[0] * d[0] + d[1] * d[1];
+    else return d[0] * d[0] + d[1] * d[1] + d[2] * d[2];
+}
+
 template <bool MSE, int C>
 __global__ void __launch_bounds__(MSE ? 1024 : 256) k_composite_train_bwd(
     const float* __restrict__ grad_weights_sum, const float* __restrict__ grad_image,
@@ -614,11 +653,16 @@ __global__ void __launch_bounds__(MSE ? 1024 : 256) k_composite_train_bwd(
 // training step needs nothing between the two compositing kernels, so the second pass over the ray's samples follows
 // the first while they are still in L2, image / weights_sum stay in registers, and one launch (and the gap before it)
 // disappears.  Same arithmetic, in the same order, as k_composite_train_fwd + k_composite_train_bwd<true>.
-template <int C>
+// Tail = MseTail: the target is finished and only the loss sum is wanted.  Tail = FrameTail: the frame term of a training
+// step -- the target is mixed here, the squared error is also written per ray, the term carries a weight; the compositing
+// loops, the blend and the zero-fill blocks are these same lines (the MseTail instantiations compile to what the
+// untemplated kernel compiled to, instruction for instruction).
+template <int C, typename Tail>
 __global__ void __launch_bounds__(1024) k_composite_train_fwd_bwd_mse(
     const float* __restrict__ sigmas, const float* __restrict__ rgbs, const float* __restrict__ deltas,
     const int32_t* __restrict__ rays, uint32_t M, uint32_t N, float* weights_sum, float* image, float* out_image,
-    float* grad_sigmas, float* grad_rgbs, MseTail mse, uint32_t ray_blocks) {
+    float* grad_sigmas, float* grad_rgbs, Tail mse, uint32_t ray_blocks) {
+    constexpr bool FRAMES = is_frame_tail<Tail>::value;
     if (blockIdx.x >= ray_blocks) {
         const uint32_t used = min((uint32_t)mse.counter[0], M);
         const uint32_t tid = (blockIdx.x - ray_blocks) * blockDim.x + threadIdx.x;
@@ -667,26 +711,55 @@ __global__ void __launch_bounds__(1024) k_composite_train_fwd_bwd_mse(
             FOR_CH(q, out_image[(size_t)index * C + q] = o[q]);
         }
     }
-    // ---- loss value (every ray contributes, marched or not)
-    if (mse.loss) {
-        __shared__ float s_err[16];
+    // ---- the frame tail's target and per-ray error (every live ray: marched, missed or dropped)
+    float tg[C];
+    FOR_CH(q, tg[q] = 0.0f);
+    if constexpr (FRAMES) {
         float e = 0.0f;
-        if (live && lane < C) {
-            float ol;                                             // o[lane]
-            if constexpr (C == 1) ol = o[0];
-            else if constexpr (C == 2) ol = lane == 0 ? o[0] : o[1];
-            else ol = lane == 0 ? o[0] : lane == 1 ? o[1] : o[2];
-            const float d = ol - mse.target[(size_t)index * C + lane];
-            e = d * d;
+        if (live) {
+            frame_gt<C>(mse, index, tg);
+            float d[C];
+            FOR_CH(q, d[q] = o[q] - tg[q]);
+            e = sq_sum<C>(d) / (float)C;
+            if (lane == 0) {
+                if (mse.gt_out) {
+                    FOR_CH(q, mse.gt_out[(size_t)index * C + q] = tg[q]);
+                }
+                if (mse.err_out) mse.err_out[index] = e;
+            }
         }
-        e += dpp_take<0x102>(0.0f, e);                        // lanes 0..2 -> lane 0 (row_shl 2, 1); lanes >= C hold 0
-        e += dpp_take<0x101>(0.0f, e);
-        if (lane == 0) s_err[threadIdx.x >> 6] = e;
-        __syncthreads();
-        if (threadIdx.x == 0) {
-            float t = 0.0f;
-            for (uint32_t w = 0; w < (blockDim.x >> 6); w++) t += s_err[w];
-            atomicAdd(mse.loss, t * mse.loss_scale);
+        if (mse.loss) {
+            __shared__ float s_err[16];
+            if (lane == 0) s_err[threadIdx.x >> 6] = e;
+            __syncthreads();
+            if (threadIdx.x == 0) {
+                float t = 0.0f;
+                for (uint32_t w = 0; w < (blockDim.x >> 6); w++) t += s_err[w];
+                atomicAdd(mse.loss, t * mse.loss_scale);
+            }
+        }
+    } else {
+        // ---- loss value (every ray contributes, marched or not)
+        if (mse.loss) {
+            __shared__ float s_err[16];
+            float e = 0.0f;
+            if (live && lane < C) {
+                float ol;                                             // o[lane]
+                if constexpr (C == 1) ol = o[0];
+                else if constexpr (C == 2) ol = lane == 0 ? o[0] : o[1];
+                else ol = lane == 0 ? o[0] : lane == 1 ? o[1] : o[2];
+                const float d = ol - mse.target[(size_t)index * C + lane];
+                e = d * d;
+            }
+            e += dpp_take<0x102>(0.0f, e);                        // lanes 0..2 -> lane 0 (row_shl 2, 1); lanes >= C hold 0
+            e += dpp_take<0x101>(0.0f, e);
+            if (lane == 0) s_err[threadIdx.x >> 6] = e;
+            __syncthreads();
+            if (threadIdx.x == 0) {
+                float t = 0.0f;
+                for (uint32_t w = 0; w < (blockDim.x >> 6); w++) t += s_err[w];
+                atomicAdd(mse.loss, t * mse.loss_scale);
+            }
         }
     }
     // ---- backward
@@ -698,7 +771,11 @@ __global__ void __launch_bounds__(1024) k_composite_train_fwd_bwd_mse(
         return;
     }
     float gi[C];
-    FOR_CH(q, gi[q] = o[q] - mse.target[(size_t)index * C + q]);
+    if constexpr (FRAMES) {
+        FOR_CH(q, gi[q] = o[q] - tg[q]);
+    } else {
+        FOR_CH(q, gi[q] = o[q] - mse.target[(size_t)index * C + q]);
+    }
     const float gsc = mse.scale_mul ? mse.scale * mse.scale_mul[0] : mse.scale;
     FOR_CH(q, gi[q] *= gsc);
     const float gws = -bg_dot<C>(gi, mse.bg, index);
@@ -717,8 +794,17 @@ __global__ void __launch_bounds__(1024) k_composite_train_fwd_bwd_mse(
         float w, T, c_i[C], ws_i;
         comp_chunk<C>(active, sigma, dl.x, dl.y, c, lane, kb, w, T, c_i, ws_i);
         if (active) {
-            FOR_CH(q, grad_rgbs[p * C + q] = gi[q] * w);
-            grad_sigmas[p] = dl.x * (colour_terms<C>(gi, T, c, c_final, c_i) + gws * (T - (ws_final - ws_i)));
+            if constexpr (FRAMES) {
+                // the term's weight multiplies the FINISHED gradients (one rounding each: a weighted call's are
+                // fl(weight * the unweighted call's)); folded into gi, its rounding would go through the cancelling sum
+                // below -- 67 ulp apart at weight 0.3 where this form is within half an ulp
+                FOR_CH(q, grad_rgbs[p * C + q] = mse.weight * (gi[q] * w));
+                grad_sigmas[p] =
+                    mse.weight * (dl.x * (colour_terms<C>(gi, T, c, c_final, c_i) + gws * (T - (ws_final - ws_i))));
+            } else {
+                FOR_CH(q, grad_rgbs[p * C + q] = gi[q] * w);
+                grad_sigmas[p] = dl.x * (colour_terms<C>(gi, T, c, c_final, c_i) + gws * (T - (ws_final - ws_i)));
+            }
         }
     }
 }
@@ -1611,12 +1697,46 @@ int enerf_composite_rays_train_fwd_bwd_mse_c(const float* sigmas, const float* r
     ENERF_COMP_BG("composite_rays_train_fwd_bwd_mse", bg_color, bg_stride, channels);
     ProfScope prof(ENERF_K_COMPOSITE_BWD, s);
     const uint32_t ray_blocks = div_up(N, 16);
-    ENERF_COMP_DISPATCH(channels, k_composite_train_fwd_bwd_mse<C><<<ray_blocks + 16, 1024, 0, s>>>(
+    ENERF_COMP_DISPATCH(channels, k_composite_train_fwd_bwd_mse<C, MseTail><<<ray_blocks + 16, 1024, 0, s>>>(
         sigmas, rgbs, deltas, rays, M, N, weights_sum, image, out_image, grad_sigmas, grad_rgbs,
         MseTail{nullptr, target, grad_scale, Background{bg_color, bg_stride, bg_scalar}, counter, loss,
                 1.0f / ((float)C * (float)N), amp_state().scale},
         ray_blocks));
     ENERF_LAUNCH_CHECK("composite_rays_train_fwd_bwd_mse");
+    return 0;
+}
+
+int enerf_composite_rays_train_fwd_bwd_frames_c(const float* sigmas, const float* rgbs, const float* deltas,
+                                                const int32_t* rays, uint32_t M, uint32_t N, float* weights_sum,
+                                                float* image, const float* bg_color, uint32_t bg_stride,
+                                                float bg_scalar, float* out_image, const float* pixels,
+                                                uint32_t pix_stride, float weight, float* gt_out, float* err_out,
+                                                const int32_t* counter, float* grad_sigmas, float* grad_rgbs,
+                                                float* loss, uint32_t channels, enerf_stream_t stream) {
+    ENERF_COMP_CHANNELS("composite_rays_train_fwd_bwd_frames", channels);
+    hipStream_t s = (hipStream_t)stream;
+    if (N == 0) {
+        if (M) {
+            (void)hipMemsetAsync(grad_sigmas, 0, (size_t)M * 4, s);
+            (void)hipMemsetAsync(grad_rgbs, 0, (size_t)M * 4 * channels, s);
+        }
+        return 0;
+    }
+    if (!counter || !pixels || !out_image || !weights_sum || !image)
+        ENERF_BADARG("composite_rays_train_fwd_bwd_frames: counter, pixels, out_image, weights_sum and image are required");
+    if (pix_stride != channels && pix_stride != channels + 1)
+        ENERF_BADARG("composite_rays_train_fwd_bwd_frames: pix_stride %u (channels or channels + 1)", (unsigned)pix_stride);
+    ENERF_COMP_BG("composite_rays_train_fwd_bwd_frames", bg_color, bg_stride, channels);
+    ProfScope prof(ENERF_K_COMPOSITE_BWD, s);
+    const uint32_t ray_blocks = div_up(N, 16);
+    // 2 / (C N) in double, rounded once: the MSE form's grad_scale as its callers round it
+    ENERF_COMP_DISPATCH(channels, k_composite_train_fwd_bwd_mse<C, FrameTail><<<ray_blocks + 16, 1024, 0, s>>>(
+        sigmas, rgbs, deltas, rays, M, N, weights_sum, image, out_image, grad_sigmas, grad_rgbs,
+        FrameTail{pixels, pix_stride, (float)(2.0 / ((double)C * (double)N)), weight,
+                  Background{bg_color, bg_stride, bg_scalar}, counter, loss, (float)((double)weight / (double)N),
+                  amp_state().scale, gt_out, err_out},
+        ray_blocks));
+    ENERF_LAUNCH_CHECK("composite_rays_train_fwd_bwd_frames");
     return 0;
 }
 

@@ -247,16 +247,30 @@ def train_step_events(model, data, opt, criterion=None, bg_color=None, bg_color_
     return loss, delta
 
 
+def frame_background(images, C, bg_color_frames=None):
+    """The frame render's background in an event step with frames (nerf/utils.py:536-540): a per-pixel draw for alpha
+    images (`bg_color_frames` replaces the draw), the renderer's default white otherwise."""
+    if images.shape[-1] == C + 1:
+        return torch.rand_like(images[..., :C]) if bg_color_frames is None else bg_color_frames
+    return 1
+
+
 def train_step_events_manual(model, data, opt, after_forward=None, bg_color=None, defer_table=False,
-                             after_mlp_backward=None, bg_color_no_evs=None):
-    """The event-only step with the two renders driven without autograd (fused_render.render_train_raw /
-    backward_raw): the losses and their image gradients come from event_loss_with_grads / no_event_loss_with_grads
-    (one launch each on the device), and the gradients are handed to the renders' closed backward.  Same values as
-    train_step_events + loss.backward() (nerf/utils.py:482-546); leaves the gradients in p.grad and returns (loss, delta).  `after_forward()` is called
-    once both forwards are queued, `after_mlp_backward()` once the second render's MLP backward kernels are."""
+                             after_mlp_backward=None, bg_color_no_evs=None, bg_color_frames=None, return_terms=False):
+    """The event step with its renders driven without autograd (fused_render.render_train_raw / backward_raw): the
+    event losses and their image gradients come from event_loss_with_grads / no_event_loss_with_grads (one launch each
+    on the device), and the gradients are handed to the renders' closed backward; with `event_only` off the frame render
+    sits third, as the reference's (its counter slot and its background draw land where the reference's do), and its loss,
+    gradient and alpha mix are formed inside its compositing launch (fused_render.backward_raw(frames=...)) with the
+    weight `weight_loss_rgb`.  Same values as train_step_events + loss.backward() (nerf/utils.py:482-567); leaves the
+    gradients in p.grad and returns (loss, delta) -- with `return_terms` a third value, the terms as the reference logs
+    them: dict(loss_evs, loss_frames (unweighted, None without the term), loss_no_evs (None without the term)).
+    `after_forward()` is called once every forward is queued, `after_mlp_backward()` once the last render's MLP backward
+    kernels are.  `bg_color` / `bg_color_frames` / `bg_color_no_evs` replace the step's draws (tests)."""
     from . import fused_network as fnet
     from . import fused_render as fr
-    B = data["images"].shape[0]
+    images = data["images"]
+    B = images.shape[0]
     dev = data["rays_evs_o1"].device
     bg = torch.rand((B, 1, opt.out_dim_color), device=dev) if bg_color is None else bg_color
     kw = {k: v for k, v in opt.render_kwargs.items() if k in ("dt_gamma", "max_steps")}
@@ -264,6 +278,15 @@ def train_step_events_manual(model, data, opt, after_forward=None, bg_color=None
     img1, ctx1 = fr.render_train_raw(model, data["rays_evs_o1"], data["rays_evs_d1"], bg, True, **kw)
     img2, ctx2 = fr.render_train_raw(model, data["rays_evs_o2"], data["rays_evs_d2"], bg, True, **kw)
     ctxs = [ctx1, ctx2]
+    frames = None
+    if not opt.event_only:
+        # the frame render (nerf/utils.py:531-546): composited by its backward call, in the launch that forms the term
+        bg_frames = frame_background(images, opt.out_dim_color, bg_color_frames)
+        _, ctxf = fr.render_train_raw(model, data["rays_o"], data["rays_d"], bg_frames, True, composite=False, **kw)
+        frames = dict(pixels=images, weight=float(opt.weight_loss_rgb),
+                      err_out=torch.empty(ctxf["N"], dtype=torch.float32, device=dev) if return_terms else None)
+        loss_frames_w = torch.zeros((), dtype=torch.float32, device=dev)
+        ctxs.append(ctxf)
     no_ev = wants_no_event_term(opt)
     if no_ev:
         # the no-event pair of renders (nerf/utils.py:548-551): same closed-form route, its own background draw
@@ -277,6 +300,9 @@ def train_step_events_manual(model, data, opt, after_forward=None, bg_color=None
     C = img1.shape[-1]
     loss, delta, g1, g2 = event_loss_with_grads(img1.view(*shape, C), img2.view(*shape, C), data["pols"], opt)
     grads = [g1, g2]
+    loss_evs, loss_no = loss, None
+    if frames is not None:
+        grads.append(None)                              # (the frame render's gradient is formed by its own backward)
     if no_ev:
         loss_no, g3, g4 = no_event_loss_with_grads(img3.view(*nshape, C), img4.view(*nshape, C), opt)
         loss = loss + loss_no
@@ -293,8 +319,12 @@ def train_step_events_manual(model, data, opt, after_forward=None, bg_color=None
     dw = None
     for i, (c, g) in enumerate(zip(ctxs, grads)):
         last = i == len(ctxs) - 1
-        g_emb, dwi = fr.backward_raw(c, g_image=g, raw=True, defer_table=total,
-                                     after_mlp=after_mlp_backward if last else None)
+        if g is None:
+            g_emb, dwi = fr.backward_raw(c, frames=frames, loss_out=loss_frames_w, raw=True, defer_table=total,
+                                         after_mlp=after_mlp_backward if last else None)
+        else:
+            g_emb, dwi = fr.backward_raw(c, g_image=g, raw=True, defer_table=total,
+                                         after_mlp=after_mlp_backward if last else None)
         if g_emb is not None:                           # the first backward's buffer; later ones add straight into it
             if emb.grad is None:                        # ... unless they could not (then they return their own)
                 emb.grad = g_emb
@@ -304,4 +334,10 @@ def train_step_events_manual(model, data, opt, after_forward=None, bg_color=None
     kind = ctx1["sv"]["kind"]
     for p, g in zip(params[1:], fnet.unpack_weight_grads(dw, ctx1["sv"]["out_c"], kind)):
         p.grad = g.view_as(p)
+    if frames is not None:
+        loss = loss + loss_frames_w                     # (complete once the frame render's backward is queued)
+    if return_terms:
+        terms = dict(loss_evs=loss_evs.detach(), loss_no_evs=loss_no,
+                     loss_frames=None if frames is None else frames["err_out"].mean())
+        return loss.detach(), delta, terms
     return loss.detach(), delta

@@ -526,9 +526,11 @@ def render_train_raw(model, rays_o, rays_d, bg_color=1, perturb=True, dt_gamma=0
 
 
 def backward_raw(ctx, g_image=None, target=None, upstream=1.0, loss_out=None, raw=False, defer_table=0,
-                 after_mlp=None):
+                 after_mlp=None, frames=None):
     """Backward half.  Either g_image = d loss / d image [N,C], or target [N,C] for loss = mean((image - target)^2) *
-    upstream (gradient and, with loss_out, value formed inside the composite backward).  -> the gradients of
+    upstream (gradient and, with loss_out, value formed inside the composite backward), or frames = dict(pixels [N, C or
+    C + 1], weight, err_out [N] or None, gt_out [N,C] or None) for the frame term (frame_term.frame_term_statement; the
+    render came from render_train_raw(composite=False), loss_out is added into).  -> the gradients of
     fused_network.network_params(model) (raw=True: (embedding gradient, flat dW), see fused_network.nerf_backward);
     the embedding gradient is None when it was added into an existing embeddings.grad."""
     N, M = ctx["N"], ctx["M"]
@@ -536,7 +538,15 @@ def backward_raw(ctx, g_image=None, target=None, upstream=1.0, loss_out=None, ra
     with torch.no_grad():
         g_sigmas = torch.empty_like(ctx["sigmas"])
         g_rgbs = torch.empty_like(ctx["rgb"])
-        if target is not None and not ctx["composited"]:
+        if frames is not None:
+            assert not ctx["composited"], "backward_raw(frames=...) needs render_train_raw(composite=False)"
+            pixels = frames["pixels"]
+            _rb.composite_rays_train_fwd_bwd_frames(ctx["sigmas"], ctx["rgb"], ctx["deltas"], ctx["rays"], M, N,
+                                                    ctx["weights_sum"], ctx["image"], ctx["bg"], ctx["out_image"],
+                                                    pixels.contiguous().view(-1, pixels.shape[-1]),
+                                                    float(frames.get("weight", 1.0)), ctx["counter"], g_sigmas, g_rgbs,
+                                                    frames.get("gt_out"), frames.get("err_out"), loss_out)
+        elif target is not None and not ctx["composited"]:
             _rb.composite_rays_train_fwd_bwd_mse(ctx["sigmas"], ctx["rgb"], ctx["deltas"], ctx["rays"], M, N,
                                                  ctx["weights_sum"], ctx["image"], ctx["bg"], ctx["out_image"],
                                                  target.contiguous().view(-1, C), 2.0 * float(upstream) / (C * N),
@@ -575,6 +585,22 @@ def train_step_mse(model, rays_o, rays_d, target, bg_color=1, perturb=True, dt_g
         after_forward()                         # e.g. prefetch_march of the next batch on a side stream
     return out_image, backward_raw(ctx, target=target, upstream=upstream, loss_out=loss_out, raw=raw,
                                    defer_table=ctx["M"] if defer_table else 0, after_mlp=after_mlp_backward)
+
+
+def train_step_frames(model, rays_o, rays_d, pixels, bg_color, weight=1.0, perturb=True, dt_gamma=0, max_steps=1024,
+                      after_forward=None, loss_out=None, raw=False, defer_table=False, after_mlp_backward=None,
+                      gt_out=None):
+    """train_step_mse's twin for the frame term (Trainer.train_step, nerf/utils.py:595-604,634): `pixels` [.., C] or, with
+    an alpha, [.., C + 1] -- mixed on `bg_color` inside the compositing launch -- and loss = weight * mean over rays of the
+    per-ray squared error.  -> (image [N,C], err [N] the per-ray error, gradients as train_step_mse returns them).
+    `loss_out` (a device scalar) has the loss ADDED; `gt_out` [N,C] receives the mixed ground truth."""
+    out_image, ctx = render_train_raw(model, rays_o, rays_d, bg_color, perturb, dt_gamma, max_steps, composite=False)
+    if after_forward is not None:
+        after_forward()
+    err = torch.empty(ctx["N"], dtype=torch.float32, device=out_image.device)
+    grads = backward_raw(ctx, frames=dict(pixels=pixels, weight=weight, err_out=err, gt_out=gt_out), loss_out=loss_out,
+                         raw=raw, defer_table=ctx["M"] if defer_table else 0, after_mlp=after_mlp_backward)
+    return out_image, err, grads
 
 
 # ---------------------------------------------------------------------------------------------------------------------

@@ -53,6 +53,9 @@ class TrainHarness:
         self.overlap_update = True    # update steps: the render's count pass is queued before the update's read-back
         self.native_step = True       # steady-state RGB steps on one GPU as ONE library call (enerf_train_step_mse)
         self.native_normalised = False  # the one-call event step also at C_thres = -1 (the normalised loss): opt-in
+        # the frame term in closed form (fused_render.train_step_frames): step_frames, and step_events with
+        # event_only = 0, leave autograd where _closed_frames_regime() and the routes' own checks hold: opt-in
+        self.closed_frames = False
         self._native_route_sig, self._native_route_dp, self._pending_sig = None, False, None
         self._params = [p for g in self.opt.param_groups for p in g["params"]]
         enc = getattr(model, "encoder", None)
@@ -700,6 +703,12 @@ class TrainHarness:
         if chunked:
             return loss
         self._reduce_grads(None if side is not None else next_rays)
+        self._optimizer_tail(fuse_table)
+        return loss
+
+    def _optimizer_tail(self, fuse_table):
+        """The optimizer step of the closed-form routes: the table's record lists straight into Adam where the backward
+        left them as lists (`fuse_table`), else Adam over the dense gradients."""
         if fuse_table:
             enc = self.model._modules["encoder"]
             emb = enc._parameters["embeddings"]
@@ -710,7 +719,6 @@ class TrainHarness:
             self._cleared_grad = self.model.encoder.embeddings.grad
         else:
             self._opt_step()
-        return loss
 
     def step_rgb(self, rays_o, rays_d, target, next_rays=None, **render_kw):
         """One RGB training step (nerf/utils.py:575-640 train_step + the optimizer part of train_one_epoch)."""
@@ -795,7 +803,8 @@ class TrainHarness:
         converted, per-ray squared error; with `sampler` and the batch's "index" / "inds_coarse" the per-ray error is
         written back into the sampler's error map.  `opt` (EventOptions-like, optional) gives out_dim_color, color_space
         and render_kwargs.  Autograd through model.render in every regime, with that regime's optimizer and scaler
-        protocol; under strat_f16 the stratified route's fp16 regime when it serves the render."""
+        protocol; under strat_f16 the stratified route's fp16 regime when it serves the render.  With `closed_frames`
+        the plain fp32 one-GPU step goes without autograd (_frames_closed_ok, _step_frames_closed)."""
         m = self.model
         C = int(getattr(opt, "out_dim_color", None) or getattr(m, "out_dim_color", 3))
         kw = dict(getattr(opt, "render_kwargs", None) or {})
@@ -805,11 +814,16 @@ class TrainHarness:
             from .evaluate import srgb_to_linear
             images = torch.cat([srgb_to_linear(images[..., :C]), images[..., C:]], dim=-1)
         bg = 1 if m.bg_radius > 0 else torch.rand_like(images[..., :C])     # (pixel-wise random, nerf/utils.py:593)
-        if images.shape[-1] == C + 1:
+        closed = self._frames_closed_ok(rays_o, rays_d, images, bg, kw)
+        if closed:
+            gt = None       # (the alpha mix, the per-ray error and the loss gradient come out of the compositing launch)
+        elif images.shape[-1] == C + 1:
             gt = images[..., :C] * images[..., C:] + bg * (1 - images[..., C:])
         else:
             gt = images
-        if self.strat_f16:
+        if closed:
+            per_ray = self._step_frames_closed(rays_o, rays_d, images, bg, kw)
+        elif self.strat_f16:
             per_ray = self._strat_f16_step(lambda: self._step_frames(rays_o, rays_d, gt, bg, kw),
                                            self._strat_f16_ok(rays_o, rays_d, kw, bg))
         elif self.amp_bf16 or self.amp_f16:
@@ -827,6 +841,59 @@ class TrainHarness:
         if self.lr_scheduler is not None:
             self.lr_scheduler.step()
         return per_ray.mean()
+
+    def _closed_frames_regime(self):
+        """Where the closed frame term may run at all: switched on, the plain fp32 regime, one GPU, no captured graphs."""
+        return (self.closed_frames and not (self.fp16 or self.amp_bf16 or self.amp_f16 or self.strat_f16)
+                and self.avg is None and not self.use_graphs and getattr(self.model, "graph_counter", None) is None)
+
+    def _frames_closed_ok(self, rays_o, rays_d, images, bg, kw):
+        """step_frames takes fused_render.train_step_frames: the regime above, fp32 pixels of C or C + 1 channels, render
+        keywords the raw render knows, a render the fused route serves (no background model: `supported` refuses)."""
+        if not (self._closed_frames_regime() and self.manual_mse and self.model.cuda_ray):
+            return False
+        from . import fused_render
+        C = fused_render.channels(self.model)
+        return (images.dtype == torch.float32 and images.device == rays_o.device and images.shape[-1] in (C, C + 1)
+                and images.shape[:-1] == rays_o.shape[:-1] and kw.get("out_dim_color", C) == C
+                and not set(kw) - {"dt_gamma", "max_steps", "out_dim_color"}
+                and fused_render.supported(self.model, rays_o.contiguous().view(-1, 3), rays_d.contiguous().view(-1, 3), bg,
+                                           kw.get("dt_gamma", 0)))
+
+    def _fresh_grads(self, defer_table):
+        """No gradient accumulates across steps -- except that the table's buffer is kept where the last Adam pass left it
+        clean (see _manual_fwd_bwd); with `defer_table` the dense part of the table's gradient gets a home."""
+        emb = self.model._modules["encoder"]._parameters["embeddings"]
+        keep = self._reuse_cleared_grad(emb)
+        for p in self._params:
+            p.grad = None
+        if keep is not None:
+            emb.grad = keep
+        elif defer_table:
+            emb.grad = torch.zeros_like(emb)
+
+    def _step_frames_closed(self, rays_o, rays_d, images, bg, kw):
+        """_step_frames without autograd (one GPU, fp32): -> the per-ray loss [B,N]; the step is taken."""
+        from . import fused_network, fused_render
+        m = self.model
+        if not m.training:
+            m.train()
+        self.maybe_update_extra_state()
+        self.global_step += 1
+        fuse_table = self.fuse_table_adam and hasattr(self.opt, "step_grid_table")
+        march = {k: kw[k] for k in ("dt_gamma", "max_steps") if k in kw}
+
+        def step(_own):
+            self._fresh_grads(fuse_table)
+            _, err, grads = fused_render.train_step_frames(m, rays_o, rays_d, images, bg, 1.0, self.perturb,
+                                                           defer_table=fuse_table, **march)
+            for p, g in zip(fused_network.network_params(m), grads):
+                if g is not None:
+                    p.grad = g.view_as(p)
+            return err
+        err = self._step_then_tail(False, step, None)
+        self._optimizer_tail(fuse_table)
+        return err.view(rays_o.shape[:-1])
 
     def _step_frames(self, rays_o, rays_d, gt, bg, kw):
         """-> the per-ray loss [B,N] fp32, detached; the step is taken."""
@@ -997,7 +1064,28 @@ class TrainHarness:
         from . import fused_render
         m = self.model
         ro, rd = data["rays_evs_o1"], data["rays_evs_d1"]
-        return (self.manual_mse and opt.event_only and m.cuda_ray
+        if not opt.event_only and not self._event_frames_closed_ok(data, opt):
+            return False
+        return (self.manual_mse and m.cuda_ray
                 and not set(opt.render_kwargs) - {"dt_gamma", "max_steps", "out_dim_color"}
                 and fused_render.supported(m, ro.contiguous().view(-1, 3), rd.contiguous().view(-1, 3), 1,
                                            opt.render_kwargs.get("dt_gamma", 0)))
+
+    def _event_frames_closed_ok(self, data, opt):
+        """event_only = 0: the frame term of the step (the default MSE criterion -- the harness passes no other) goes the
+        closed route too: the regime of _closed_frames_regime, fp32 frames without alpha or, at three channels, with one
+        (train_step_events tells alpha images by their four channels, as the reference does), frame rays the fused
+        render serves with the background they will get."""
+        if not self._closed_frames_regime():
+            return False
+        from . import fused_render
+        images, C = data["images"], int(opt.out_dim_color)
+        if not (images.dtype == torch.float32 and images.device == data["rays_o"].device
+                and C == fused_render.channels(self.model)
+                and opt.render_kwargs.get("out_dim_color", C) == C
+                and (images.shape[-1] == C or (C == 3 and images.shape[-1] == 4))
+                and images.shape[:-1] == data["rays_o"].shape[:-1]):
+            return False
+        bg = torch.empty_like(images[..., :C]) if images.shape[-1] == C + 1 else 1
+        return fused_render.supported(self.model, data["rays_o"].contiguous().view(-1, 3),
+                                      data["rays_d"].contiguous().view(-1, 3), bg, opt.render_kwargs.get("dt_gamma", 0))

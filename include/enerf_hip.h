@@ -71,7 +71,9 @@ const char* enerf_last_error(void);
  *     Still 13: enerf_debug_sigma_head added (a testing aid: the density-only head's load pipeline against the form shipped
  *     before) -- no signature changed, and tests/test_composite_channels_host.py holds the header at 13.
  *     Still 13: enerf_no_event_loss_fwd_bwd_c added, and enerf_event_loss_fwd_bwd_c serves C_thres == -1 (the normalised
- *     loss) where it answered ENERF_E_BADARG -- nothing existing changed meaning or layout. */
+ *     loss) where it answered ENERF_E_BADARG -- nothing existing changed meaning or layout.
+ *     Still 13: enerf_composite_rays_train_fwd_bwd_frames_c added (the frame term's compositing) -- a new
+ *     symbol beside the old ones; two test files hold the header at 13. */
 #define ENERF_ABI_VERSION 13
 int enerf_abi_version(void);
 /* The library keeps grow-only scratch buffers per device (march chunk log, grid-backward record lists, ...).  Growing one
@@ -283,6 +285,31 @@ int enerf_composite_rays_train_fwd_bwd_mse_c(const float* sigmas, const float* r
                                              float* out_image, const float* target, float grad_scale,
                                              const int32_t* counter, float* grad_sigmas, float* grad_rgbs, float* loss,
                                              uint32_t channels, enerf_stream_t stream);
+
+/* enerf_composite_rays_train_fwd_bwd_mse_c with a FRAME tail in place of the finished target: the frame term of
+ * Trainer.train_step (nerf/utils.py:595-604,634) and of train_step_events with event_only = 0 (:546), formed in the
+ * launch.  Per ray (indexed by the ray id rays[n][0], as everything here):
+ *   gt       = pixels[ray]                                    (pix_stride == channels), or
+ *              fl(fl(p a) + fl(bg fl(1 - a))), a = pixels[ray][channels]   (pix_stride == channels + 1: alpha images,
+ *              mixed on THIS call's background at that ray -- bit for bit torch's images[..., :C] * a + bg * (1 - a));
+ *   err      = sum_c (out_image - gt)^2 / channels            for every ray: marched, missed or dropped;
+ *   loss    += weight * sum_rays err / N                      (one float atomic per workgroup; the caller zeroes it);
+ *   g_image  = 2 / (channels N) * (out_image - gt)            (times the loss scale between enerf_amp_begin / _end),
+ * and from g_image on everything is the MSE form's: weights_sum / image / out_image written, grad_sigmas / grad_rgbs may
+ * be UNINITIALISED -- with `weight` multiplied into the finished grad_sigmas / grad_rgbs, one rounding each (d sigma is a
+ * sum that cancels: a weight folded into g_image sends its rounding through that sum, 67 ulp at weight 0.3; this way a
+ * weighted call's gradients are fl(weight * the unweighted call's)).  With pix_stride == channels and weight == 1 the
+ * images and gradients equal those of
+ * enerf_composite_rays_train_fwd_bwd_mse_c(target = pixels, grad_scale = 2 / (channels N)) bit for bit.
+ * gt_out [N,channels], err_out [N], loss: optional.  pix_stride outside {channels, channels + 1}, or counter / pixels /
+ * weights_sum / image / out_image == NULL: ENERF_E_BADARG.  N == 0: the gradients are zero-filled, nothing else. */
+int enerf_composite_rays_train_fwd_bwd_frames_c(const float* sigmas, const float* rgbs, const float* deltas,
+                                                const int32_t* rays, uint32_t M, uint32_t N, float* weights_sum,
+                                                float* image, const float* bg_color, uint32_t bg_stride,
+                                                float bg_scalar, float* out_image, const float* pixels,
+                                                uint32_t pix_stride, float weight, float* gt_out, float* err_out,
+                                                const int32_t* counter, float* grad_sigmas, float* grad_rgbs,
+                                                float* loss, uint32_t channels, enerf_stream_t stream);
 
 /* raymarching.cu:807-813  march_rays(n_alive, n_step, rays_alive, rays_t, rays_o, rays_d, bound, dt_gamma,
  *                                    max_steps, C, H, grid, nears, fars, xyzs, dirs, deltas, perturb) */
