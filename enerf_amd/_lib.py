@@ -110,6 +110,7 @@ SIGNATURES = {
     "enerf_event_loss_fwd_bwd": [_vp, _vp, _vp, _u32, _u32, _u32, _f32, _f32, _f32, _vp, _vp, _vp, _vp, _vp],
     "enerf_event_loss_fwd_bwd_c": [_vp, _vp, _vp, _u32, _u32, _u32, _f32, _f32, _f32, _vp, _vp, _vp, _vp, _u32, _vp],
     "enerf_no_event_loss_fwd_bwd_c": [_vp, _vp, _u32, _u32, _f32, _f32, _vp, _vp, _vp, _u32, _vp],
+    "enerf_event_c_estimate": [_vp, _vp, _u32, _u32, _vp, _vp, _vp],
     "enerf_event_pair_rays": [_vp, _vp, _vp, _vp, _u32, _vp, _vp, _u32, _u32, _vp, _vp, _vp, _vp, _u32, _f32, _f32, _f32,
                               _f32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
     "enerf_event_single_pair_rays": [_vp, _u32, _vp, _vp, _u32, _vp, _vp, _u32, _vp, _vp, _vp, _vp, _u32, _f32, _f32, _f32,

@@ -375,6 +375,136 @@ __global__ void __launch_bounds__(1024) k_no_event_loss(const float* __restrict_
     block_sums_1024<1>(acc, part);
     if (threadIdx.x == 0 && loss) loss[0] = (float)((double)c.upstream * acc[0] / count);
 }
+
+// ---- the implicit contrast threshold (utils/event_utils.py:69-107 with its documented (N,1) / (N,C) shapes) -------------
+// Four medians of delta[i,k] / pol[i]: over the positive events, the negative ones, and the sign-consistent subsets of
+// both.  One workgroup per class; a radix select, 8 bits per pass, over keys that order like the floats: each of the four
+// passes recomputes the quotients from delta and pols (no scratch buffer), counts the candidates -- the values that share
+// the digits found so far -- per next digit, and picks the digit that holds the wanted rank.  After four passes the key IS
+// the value of rank (count - 1) / 2, torch.median's lower middle.  Counting is integer adds into LDS, so the answer does
+// not depend on their order.  Early in training most deltas are exactly 0 and every key lands in one bin: each wave owns a
+// private histogram, and the lanes that share the first taker's bin add once, together (c_hist_add).
+__device__ __forceinline__ uint32_t c_key(float v) {                 // -inf < ... < -0 < +0 < ... < +inf, ascending
+    const uint32_t u = __float_as_uint(v);
+    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+}
+__device__ __forceinline__ float c_unkey(uint32_t k) {
+    return __uint_as_float((k & 0x80000000u) ? (k & 0x7fffffffu) : ~k);
+}
+// h: the wave's own 256 bins.  The takers that share the first taker's bin add once, by their first lane; the others
+// add for themselves.  (The votes count the lanes inside the branch only.)
+__device__ __forceinline__ void c_hist_add(uint32_t* h, bool take, uint32_t bin, uint32_t lane) {
+    if (take) {
+        const uint32_t b0 = (uint32_t)__builtin_amdgcn_readfirstlane((int)bin);
+        const unsigned long long same = __ballot(bin == b0);
+        if (bin != b0) atomicAdd(&h[bin], 1u);
+        else if (lane == (uint32_t)__ffsll(same) - 1u) atomicAdd(&h[b0], (uint32_t)__popcll(same));
+    }
+}
+__device__ __forceinline__ bool c_member(uint32_t cls, float pol, float d0) {
+    // (a NaN pol fails both comparisons; a NaN d0 fails both sign conditions, as in torch)
+    const bool on = pol > 0.0f, off = pol < 0.0f;
+    return cls == 0u ? on : cls == 1u ? off : cls == 2u ? (on && d0 >= 0.0f) : (off && d0 <= 0.0f);
+}
+template <int CH>
+__global__ void __launch_bounds__(1024) k_event_c_estimate(const float* __restrict__ delta, const float* __restrict__ pols,
+                                                           uint32_t N, float* __restrict__ medians,
+                                                           uint32_t* __restrict__ counts) {
+    __shared__ uint32_t hist[16][256];
+    __shared__ uint32_t tot[256];
+    __shared__ uint32_t meta[2];                                     // the class's count, whether it holds a NaN
+    __shared__ uint32_t sel[2];                                      // the pass's digit, the rank within it
+    // events a thread loads before it counts the first: a step's 20 096 pairs are one round of loads per pass
+    constexpr int kUnroll = CH == 1 ? 24 : 16;
+    const uint32_t cls = blockIdx.x, tid = threadIdx.x, wave = tid >> 6, lane = tid & 63u;
+    uint32_t prefix = 0u, rank = 0u, count = 0u;
+    for (int pass = 0; pass < 4; pass++) {
+        const uint32_t shift = 24u - 8u * (uint32_t)pass;
+        const uint32_t found = pass == 0 ? 0u : (0xffffffffu << (shift + 8u));   // the key bits earlier passes fixed
+        for (uint32_t j = tid; j < 16u * 256u; j += 1024u) (&hist[0][0])[j] = 0u;
+        if (pass == 0 && tid < 2u) meta[tid] = sel[tid] = 0u;
+        __syncthreads();
+        uint32_t n_mine = 0u;
+        bool nan_mine = false;
+        // (wave-uniform trip count: every lane votes.  kUnroll events per thread are loaded before the first is counted:
+        //  the loop is bound by the loads' latency, not by their bytes)
+        for (uint32_t base = 0; base < N; base += 1024u * kUnroll) {
+            float pol[kUnroll], d[kUnroll][CH];
+#pragma unroll
+            for (int u = 0; u < kUnroll; u++) {
+                const uint32_t i = base + (uint32_t)u * 1024u + tid; // (the entry point keeps N + 65536 below 2^32)
+                const bool valid = i < N;
+                pol[u] = valid ? pols[i] : 0.0f;                     // (a polarity of 0 is in no class)
+                for (int k = 0; k < CH; k++) d[u][k] = valid ? delta[(size_t)i * CH + k] : 0.0f;
+            }
+#pragma unroll
+            for (int u = 0; u < kUnroll; u++) {
+                const bool member = c_member(cls, pol[u], d[u][0]);
+                for (int k = 0; k < CH; k++) {
+                    const float q = d[u][k] / pol[u];                // IEEE division (no fast-math in this build)
+                    const bool isnan = q != q;
+                    const uint32_t key = c_key(q);
+                    const bool take = member && !isnan && ((key ^ prefix) & found) == 0u;
+                    c_hist_add(hist[wave], take, (key >> shift) & 255u, lane);
+                    if (pass == 0) {
+                        n_mine += member ? 1u : 0u;
+                        nan_mine = nan_mine || (member && isnan);
+                    }
+                }
+            }
+        }
+        if (pass == 0) {
+            for (int o = 32; o > 0; o >>= 1) n_mine += (uint32_t)__shfl_down((int)n_mine, o, 64);
+            const bool any_nan = __ballot(nan_mine) != 0ull;
+            if (lane == 0u) {
+                atomicAdd(&meta[0], n_mine);
+                if (any_nan) atomicOr(&meta[1], 1u);
+            }
+        }
+        __syncthreads();
+        if (tid < 256u) {
+            uint32_t t = 0u;
+            for (int w = 0; w < 16; w++) t += hist[w][tid];
+            tot[tid] = t;
+        }
+        __syncthreads();
+        if (pass == 0) {
+            count = meta[0];
+            if (count == 0u || meta[1] != 0u) {                      // (the same for every thread of the workgroup)
+                if (tid == 0u) {
+                    medians[cls] = count == 0u ? 0.0f : __uint_as_float(0x7fc00000u);
+                    if (counts) counts[cls] = count;
+                }
+                return;
+            }
+            rank = (count - 1u) >> 1;
+        }
+        if (wave == 0u) {                                            // the bin that holds `rank`: 4 bins per lane, one scan
+            uint32_t a[4], s = 0u;
+            for (int j = 0; j < 4; j++) { a[j] = tot[4u * lane + j]; s += a[j]; }
+            uint32_t incl = s;
+            for (int o = 1; o < 64; o <<= 1) {
+                const uint32_t t = (uint32_t)__shfl_up((int)incl, o, 64);
+                if (lane >= (uint32_t)o) incl += t;
+            }
+            const uint32_t excl = incl - s;
+            if (rank >= excl && rank < incl) {                       // (exactly one lane: rank < the candidates' number)
+                uint32_t r = rank - excl;
+                for (int j = 0; j < 4; j++) {
+                    if (r < a[j]) { sel[0] = 4u * lane + j; sel[1] = r; break; }
+                    r -= a[j];
+                }
+            }
+        }
+        __syncthreads();
+        prefix |= sel[0] << shift;
+        rank = sel[1];
+    }
+    if (tid == 0u) {
+        medians[cls] = c_unkey(prefix);
+        if (counts) counts[cls] = count;
+    }
+}
 }  // namespace
 
 extern "C" int enerf_event_pair_rays(const float* events, const uint8_t* no_successor, const int64_t* num_successor,
@@ -492,5 +622,20 @@ extern "C" int enerf_no_event_loss_fwd_bwd_c(const float* image1, const float* i
     else
         k_no_event_loss<3><<<1, 1024, 0, s>>>(image1, image2, N, c, C_no, grad_image1, grad_image2, loss);
     ENERF_LAUNCH_CHECK("no_event_loss_fwd_bwd");
+    return 0;
+}
+
+extern "C" int enerf_event_c_estimate(const float* delta, const float* pols, uint32_t N, uint32_t channels, float* medians,
+                                      uint32_t* counts, enerf_stream_t stream) {
+    if (channels < 1u || channels > 3u) ENERF_BADARG("event_c_estimate: %u colour channels (1..3 are served)", channels);
+    if ((uint64_t)N * channels > 0xffff0000ull)
+        ENERF_BADARG("event_c_estimate: %u events x %u channels do not fit 32-bit counts", N, channels);
+    if (N > 0 && (!delta || !pols || !medians)) ENERF_BADARG("event_c_estimate: delta, pols and medians are required");
+    if (!medians) return 0;                                          // (N == 0 and nowhere to write the zeros)
+    const hipStream_t s = (hipStream_t)stream;
+    if (channels == 1u) k_event_c_estimate<1><<<4, 1024, 0, s>>>(delta, pols, N, medians, counts);
+    else if (channels == 2u) k_event_c_estimate<2><<<4, 1024, 0, s>>>(delta, pols, N, medians, counts);
+    else k_event_c_estimate<3><<<4, 1024, 0, s>>>(delta, pols, N, medians, counts);
+    ENERF_LAUNCH_CHECK("event_c_estimate");
     return 0;
 }

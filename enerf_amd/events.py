@@ -212,10 +212,12 @@ def no_event_loss_with_grads(image1, image2, opt):
     return loss.detach(), g1, g2
 
 
-def train_step_events(model, data, opt, criterion=None, bg_color=None, bg_color_no_evs=None):
+def train_step_events(model, data, opt, criterion=None, bg_color=None, bg_color_no_evs=None, return_terms=False):
     """One event training step's forward: two renders (+ optional frame render, + optional no-event pair of renders)
-    -> loss.  nerf/utils.py:482-573.  `bg_color` / `bg_color_no_evs` [B,1,C] replace the step's random background draws
-    (tests)."""
+    -> (loss, delta).  nerf/utils.py:482-573.  `bg_color` / `bg_color_no_evs` [B,1,C] replace the step's random
+    background draws (tests).  With `return_terms` a third value, the terms as the reference logs them (its
+    `losses_indiv`): dict(loss_evs, loss_frames (unweighted, None without the term), loss_no_evs (None without the
+    term)), detached -- the same dict train_step_events_manual hands out."""
     images = data["images"]
     B = images.shape[0]
     dev = data["rays_evs_o1"].device
@@ -227,6 +229,7 @@ def train_step_events(model, data, opt, criterion=None, bg_color=None, bg_color_
     out1 = model.render(data["rays_evs_o1"], data["rays_evs_d1"], staged=False, bg_color=bg, perturb=True, **kw)
     out2 = model.render(data["rays_evs_o2"], data["rays_evs_d2"], staged=False, bg_color=bg, perturb=True, **kw)
     loss, delta = event_loss(out1["image"], out2["image"], data["pols"], opt)
+    terms = dict(loss_evs=loss.detach(), loss_frames=None, loss_no_evs=None)
     if not opt.event_only:
         C = images.shape[-1]
         if C == 4:
@@ -237,13 +240,19 @@ def train_step_events(model, data, opt, criterion=None, bg_color=None, bg_color_
             bg_color, gt = None, images
         out = model.render(data["rays_o"], data["rays_d"], staged=False, bg_color=bg_color, perturb=True, **kw)
         crit = criterion if criterion is not None else torch.nn.MSELoss(reduction="none")
-        loss = loss + opt.weight_loss_rgb * crit(out["image"], gt).mean()
+        loss_frames = crit(out["image"], gt).mean()
+        terms["loss_frames"] = loss_frames.detach()
+        loss = loss + opt.weight_loss_rgb * loss_frames
     if wants_no_event_term(opt):
         # two more renders at pixels / times without events, a fresh background draw (nerf/utils.py:548-565)
         bg_no = torch.rand((B, 1, opt.out_dim_color), device=dev) if bg_color_no_evs is None else bg_color_no_evs
         n1 = model.render(data["rays_no_evs_o1"], data["rays_no_evs_d1"], staged=False, bg_color=bg_no, perturb=True, **kw)
         n2 = model.render(data["rays_no_evs_o2"], data["rays_no_evs_d2"], staged=False, bg_color=bg_no, perturb=True, **kw)
-        loss = loss + no_event_loss(n1["image"], n2["image"], opt)
+        loss_no = no_event_loss(n1["image"], n2["image"], opt)
+        terms["loss_no_evs"] = loss_no.detach()
+        loss = loss + loss_no
+    if return_terms:
+        return loss, delta, terms
     return loss, delta
 
 

@@ -135,6 +135,7 @@ class TrainHarness:
         self.epoch = 1
         self.stats = {"loss": [], "valid_loss": [], "results": [], "checkpoints": [], "best_result": None}
         self.lr_scheduler = None      # set_lr_scheduler(): stepped after every optimizer step (main_nerf.py:212,214)
+        self._log = None              # the TrainLog of the epoch under way (train_one_epoch(log=...)), else None
         self.use_graphs = bool(use_graphs)
         self._graphs = {}
         self._graph_generation = 0
@@ -279,14 +280,22 @@ class TrainHarness:
         return harness_render_path(self, poses, intrinsics, H, W, opt, outdir, normalize=normalize,
                                    write_behind=write_behind)
 
-    def train_one_epoch(self, sampler, opt, order=None):
-        """The reference's Trainer.train_one_epoch (nerf/utils.py:920-1015) without its logging: one step per batch of
+    def train_one_epoch(self, sampler, opt, order=None, log=None):
+        """The reference's Trainer.train_one_epoch (nerf/utils.py:920-1015); its logging with `log`: one step per batch of
         `sampler` (a FrameSampler or an EventSampler) in `order` (default: torch.randperm(len(sampler)) from torch's
         global CPU generator, the DataLoader(shuffle=True) of the reference) -- step_events for a batch with
         "rays_evs_o1", step_frames otherwise; the next batch is drawn before the current step is taken, so that the event
         route can march it underneath.  The losses are summed on the device in fp64, in step order (the reference's
         Python-float sum of fp32 losses), and read back once.  After the last step the average, if there is one, is
-        updated; -> the epoch's mean loss, also appended to stats["loss"].  `self.epoch` is train()'s to move."""
+        updated; -> the epoch's mean loss, also appended to stats["loss"].  `self.epoch` is train()'s to move.
+        `log` (a train_log.TrainLog; None, the default: no step does anything it would not do otherwise): every step writes
+        one row of the log's device ring -- the loss, an event step's terms and the implicit contrast threshold of its
+        delta and polarities (event_diag.estimate_C_thres), by launches on the step's stream and no read-back -- and the
+        ring is read back once, by log.flush() when the epoch ends.  A logged event step does not take the captured-graph
+        route (`use_graphs`), which hands out nothing but the loss: it takes the next route that serves it.  Rank 0 logs
+        its own batch; on other ranks the log is ignored."""
+        if log is not None and not log.active:
+            log = None
         if order is None:
             order = torch.randperm(len(sampler))
         order = [int(i) for i in (order.tolist() if torch.is_tensor(order) else order)]
@@ -294,15 +303,27 @@ class TrainHarness:
             raise ValueError("train_one_epoch: an empty epoch")
         total = None
         data = sampler.batch([order[0]])
-        for k in range(len(order)):
-            nxt = sampler.batch([order[k + 1]]) if k + 1 < len(order) else None
-            if "rays_evs_o1" in data:
-                loss = self.step_events(data, opt, nxt if nxt is not None and "rays_evs_o1" in nxt else None)
-            else:
-                loss = self.step_frames(data, opt, sampler)
-            loss = loss.detach().double()
-            total = loss.clone() if total is None else total.add_(loss)
-            data = nxt
+        if log is not None:
+            log.begin(len(order), next(self.model.parameters()).device)
+        self._log = log
+        try:
+            for k in range(len(order)):
+                nxt = sampler.batch([order[k + 1]]) if k + 1 < len(order) else None
+                if "rays_evs_o1" in data:
+                    loss = self.step_events(data, opt, nxt if nxt is not None and "rays_evs_o1" in nxt else None)
+                else:
+                    loss = self.step_frames(data, opt, sampler)
+                    if log is not None:
+                        log.frame_step(loss)
+                if log is not None:                     # (the lr after this step's scheduler step, as the reference logs it)
+                    log.end_step(self.global_step, self.epoch, self.opt.param_groups[0]["lr"])
+                loss = loss.detach().double()
+                total = loss.clone() if total is None else total.add_(loss)
+                data = nxt
+        finally:
+            self._log = None
+        if log is not None:
+            log.flush()
         if self.ema is not None:
             self.ema.update()
         mean = float(total) / len(order)
@@ -310,14 +331,15 @@ class TrainHarness:
         return mean
 
     def train(self, sampler, opt, max_epochs, valid_views=None, eval_interval=10, workspace=None, name="ngp",
-              max_keep_ckpt=2):
+              max_keep_ckpt=2, log=None):
         """The reference's Trainer.train (nerf/utils.py:734-761): for every epoch from `self.epoch` to `max_epochs`,
         train_one_epoch; with a `workspace`, on rank 0, a full checkpoint {workspace}/checkpoints/{name}_ep{epoch:04d}.pth,
         recorded in stats["checkpoints"], the oldest beyond `max_keep_ckpt` deleted (:1323-1329); every `eval_interval`
         epochs, with `valid_views`, evaluate() -- its valid_loss appended to stats["valid_loss"] and stats["results"] (the
         reference's default use_loss_as_metric=True) -- and the "best" checkpoint {workspace}/checkpoints/{name}.pth.
         Marking the cells no training camera sees (model.mark_untrained_grid, which the reference calls here) stays the
-        caller's job, as for every other entry point of the harness.  -> stats."""
+        caller's job, as for every other entry point of the harness.  `log`: every epoch's train_one_epoch(log=log); the
+        log is not part of a checkpoint.  -> stats."""
         import os
         import torch.distributed as dist
         rank0 = not (dist.is_available() and dist.is_initialized()) or dist.get_rank() == 0
@@ -328,7 +350,7 @@ class TrainHarness:
                 os.makedirs(ckpt_dir, exist_ok=True)
         for epoch in range(self.epoch, max_epochs + 1):
             self.epoch = epoch
-            self.train_one_epoch(sampler, opt)
+            self.train_one_epoch(sampler, opt, log=log)
             if ckpt_dir is not None and rank0:
                 path = os.path.join(ckpt_dir, f"{name}_ep{epoch:04d}.pth")
                 kept = self.stats["checkpoints"]
@@ -972,7 +994,9 @@ class TrainHarness:
         self.global_step += 1
         from .events import wants_no_event_term
         no_ev = wants_no_event_term(opt)                 # two more renders per step: neither graphs nor the one-call step
-        if opt.event_only and not no_ev and self._graphable(data["rays_evs_o1"], data["rays_evs_d1"]):
+        log = self._log                                  # (a logged step wants the terms and delta: not a graph's to give)
+        if (log is None and opt.event_only and not no_ev
+                and self._graphable(data["rays_evs_o1"], data["rays_evs_d1"])):
             names = ("images", "rays_evs_o1", "rays_evs_d1", "rays_evs_o2", "rays_evs_d2", "pols")
             key = self._graph_key("events", data["rays_evs_o1"])
             inputs = tuple(data[n] for n in names)
@@ -984,7 +1008,9 @@ class TrainHarness:
             # the shipped configs' fp16 = True around the event step (nerf/utils.py:964-975): autocast + GradScaler
             self.opt.zero_grad(set_to_none=True)
             with torch.autocast("cuda", dtype=torch.float16, enabled=self._f16_autocast):
-                loss, _ = train_step_events(self.model, data, opt)
+                loss, *rest = train_step_events(self.model, data, opt, return_terms=log is not None)
+            if log is not None:
+                log.event_step(loss, rest[0], data["pols"], rest[1])
             self.scaler.scale(loss).backward()
             self.scaler.unscale_(self.opt)
             if self.avg is not None:
@@ -1012,8 +1038,11 @@ class TrainHarness:
                 emb.grad = None
             try:
                 tail = self.prefetch_at == "mlp_backward"
-                loss, _ = train_step_events_manual(self.model, data, opt, after_forward=None if tail else side,
-                                                   after_mlp_backward=side if tail else None, defer_table=fuse_table)
+                loss, *rest = train_step_events_manual(self.model, data, opt, after_forward=None if tail else side,
+                                                       after_mlp_backward=side if tail else None,
+                                                       defer_table=fuse_table, return_terms=log is not None)
+                if log is not None:
+                    log.event_step(loss, rest[0], data["pols"], rest[1])
             except BaseException:
                 self._discard_pending_records()
                 raise
@@ -1026,7 +1055,9 @@ class TrainHarness:
                 self._opt_step()
             return loss
         self.opt.zero_grad(set_to_none=True)
-        loss, _ = train_step_events(self.model, data, opt)
+        loss, *rest = train_step_events(self.model, data, opt, return_terms=log is not None)
+        if log is not None:
+            log.event_step(loss, rest[0], data["pols"], rest[1])
         loss.backward()
         if self.avg is not None:
             self.avg()
@@ -1053,10 +1084,14 @@ class TrainHarness:
                 and getattr(m, "_last_march_event", None) is None):
             fused_render.stage_ring_copy(m)     # (the window's last step, marches on this stream: see _step_rgb_native)
         try:
-            loss, _ = fused_render.train_step_events_native(m, data, opt, self.opt, next_data=nxt, side_stream=self._side)
+            loss, delta = fused_render.train_step_events_native(m, data, opt, self.opt, next_data=nxt, side_stream=self._side)
         except BaseException:
             self._discard_pending_records()
             raise
+        if self._log is not None:
+            # on the one-call step loss_evs IS the loss; `delta` is the step context's buffer, which the next step of this
+            # shape overwrites: the estimate is queued now, on the step's stream
+            self._log.event_step(loss, delta, data["pols"], dict(loss_evs=loss))
         self._cleared_grad = emb.grad
         return loss
 

@@ -73,7 +73,9 @@ const char* enerf_last_error(void);
  *     Still 13: enerf_no_event_loss_fwd_bwd_c added, and enerf_event_loss_fwd_bwd_c serves C_thres == -1 (the normalised
  *     loss) where it answered ENERF_E_BADARG -- nothing existing changed meaning or layout.
  *     Still 13: enerf_composite_rays_train_fwd_bwd_frames_c added (the frame term's compositing) -- a new
- *     symbol beside the old ones; two test files hold the header at 13. */
+ *     symbol beside the old ones; two test files hold the header at 13.
+ *     Still 13: enerf_event_c_estimate added (the implicit contrast threshold's four medians) -- a new
+ *     symbol, nothing existing changed. */
 #define ENERF_ABI_VERSION 13
 int enerf_abi_version(void);
 /* The library keeps grow-only scratch buffers per device (march chunk log, grid-backward record lists, ...).  Growing one
@@ -754,6 +756,18 @@ int enerf_event_loss_fwd_bwd_c(const float* image1, const float* image2, const f
 int enerf_no_event_loss_fwd_bwd_c(const float* image1, const float* image2, uint32_t N, uint32_t use_luma, float C_no,
                                   float upstream, float* grad_image1, float* grad_image2, float* loss, uint32_t channels,
                                   enerf_stream_t stream);
+
+/* The implicit contrast threshold of an event step (utils/event_utils.py:69-107 estimate_C_thres_from_pol_dL with its
+ * documented (N,1) / (N,C) shapes), one launch, nothing read back: delta [N,channels] (the event loss's delta), pols [N]
+ * -> medians [4] of delta[i,k] / pols[i] over the classes  on: pol > 0;  off: pol < 0;  on_sign: pol > 0 and
+ * delta[i,0] >= 0;  off_sign: pol < 0 and delta[i,0] <= 0  (an event with pol == 0 or a NaN pol is in no class; a NaN
+ * delta[i,0] fails both sign conditions).  A class's values are the quotients of all its events' channels, counts [4]
+ * (may be NULL) their number.  Median as torch.median: the value of rank (count - 1) / 2, ascending; NaN when the class
+ * holds a NaN; 0 for an empty class.  The quotient is the correctly rounded fp32 one.  No luma is formed (the reference
+ * forms one when N == 3 -- the caller's business).  N == 0: four zeros and zero counts.  channels outside 1..3, N *
+ * channels above 2^32 - 65536, or a NULL among delta / pols / medians with N > 0: ENERF_E_BADARG.  The same bits on every run. */
+int enerf_event_c_estimate(const float* delta, const float* pols, uint32_t N, uint32_t channels, float* medians,
+                           uint32_t* counts, enerf_stream_t stream);
 
 /* One fused Adam update (torch.optim.Adam semantics, no weight decay / amsgrad) of a contiguous fp32 tensor:
  * reads p, g, m, v once and writes p, m, v (and g = 0 when zero_grad != 0).  `step` counts from 1. */
