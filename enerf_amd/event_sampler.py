@@ -25,7 +25,8 @@ from .events import get_event_rays
 
 
 def build_event_tables(events):
-    """events [E, 4] float tensor, columns (x, y, t_ns, polarity), any order.
+    """events [E, 4] float tensor, columns (x, y, t_ns, polarity), any order.  Integer coordinates only (the pixel key
+    truncates them): the events of a rectified camera go through event_dataset.EventStream.
 
     provider.py:1152-1199: sort by time; group by pixel in order of each pixel's first event, events of a pixel in
     time order; drop pixels with a single event; flatten.  Returns a dict of tensors on events.device:
@@ -406,6 +407,35 @@ class EventSampler:
         else:
             self.generator.manual_seed(int(seed))
             self.host_generator.manual_seed(int(seed))
+
+    @classmethod
+    def from_stream(cls, stream, centres_us, track, intrinsics_evs, batch_size_evs, accumulate_evs=0, acc_max_num_evs=0,
+                    negative_event_sampling=0, shrink_us=0, frames=None, seed=None):
+        """The sampler of a raw stream (event_dataset.EventStream), as EventNeRFDataset.__init__ and
+        load_events_at_frame_idxs prepare it (provider.py:1107-1362): frame i takes the events of
+        [centres_us[i] + shrink_us, centres_us[i + 1] - shrink_us) (event_dataset.event_centres) and, with
+        `negative_event_sampling`, the no-event tables of the unshrunk span [centres_us[i], centres_us[i + 1]).  `seed`
+        also seeds the no-event subsampling.  The other arguments are the constructor's."""
+        centres = [float(c) for c in centres_us]
+        if len(centres) < 2:
+            raise ValueError("EventSampler.from_stream: two window borders at least")
+        generator = None
+        if seed is not None:
+            generator = torch.Generator(device=stream.device).manual_seed(int(seed))
+        tables, no_events = [], []
+        for i in range(len(centres) - 1):
+            t0, t1 = centres[i] + shrink_us, centres[i + 1] - shrink_us
+            win = stream.window(t0, t1) if t0 < t1 else None
+            if win is None:
+                raise ValueError(f"EventSampler.from_stream: the stream does not cover frame {i}'s window [{t0}, {t1}) us")
+            if negative_event_sampling:
+                tab, nev = stream.batch_tables(win[0], win[1], centres[i], centres[i + 1], generator=generator)
+                no_events.append(nev)
+            else:
+                tab = stream.tables(win[0], win[1])
+            tables.append(tab)
+        return cls(tables, track, intrinsics_evs, batch_size_evs, accumulate_evs, acc_max_num_evs,
+                   no_events if negative_event_sampling else None, frames, seed)
 
     def __len__(self):
         """The number of event batches: one step each per epoch (TrainHarness.train_one_epoch)."""

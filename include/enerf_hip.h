@@ -75,7 +75,9 @@ const char* enerf_last_error(void);
  *     Still 13: enerf_composite_rays_train_fwd_bwd_frames_c added (the frame term's compositing) -- a new
  *     symbol beside the old ones; two test files hold the header at 13.
  *     Still 13: enerf_event_c_estimate added (the implicit contrast threshold's four medians) -- a new
- *     symbol, nothing existing changed. */
+ *     symbol, nothing existing changed.
+ *     Still 13: enerf_event_tables_workspace / _count / _fill and enerf_no_event_coords added (a raw event stream to the
+ *     pair kernels' tables) -- new symbols, nothing existing changed. */
 #define ENERF_ABI_VERSION 13
 int enerf_abi_version(void);
 /* The library keeps grow-only scratch buffers per device (march chunk log, grid-backward record lists, ...).  Growing one
@@ -725,6 +727,55 @@ int enerf_no_event_rays(const float* coords, uint32_t n_coords, const int64_t* i
                         const double* tcoef, uint32_t K, float fx, float fy, float cx, float cy, float* rays_o1,
                         float* rays_d1, float* rays_o2, float* rays_d2, double* tss_out, int32_t* outside_track,
                         int32_t* bad_index, enerf_stream_t stream);
+
+/* From a raw event stream to the tables above (csrc/event_tables.hip): the grouping loop of
+ * EventNeRFDataset.__init__ (nerf/provider.py:1152-1199) and the no-event search of load_events_at_frame_idxs
+ * (provider.py:1283-1351), keyed on the SENSOR pixel y * W + x.  The stream, all on the device: x, y u16 [>= last] sensor
+ * pixel; t i64, ascending, in stream units; p i8 polarity (+1 where p > 0, -1 otherwise: serves 0/1 and -1/+1 files).  A
+ * call works on the window [first, last) of 1 .. 2^30 events; H * W <= 2^26, H, W <= 65536.  Event time in nanoseconds:
+ * t_ns = (double)(t + t_offset) * ns_per_unit (the sum in int64, one rounded product).
+ *
+ * enerf_event_tables_workspace: *bytes = size of the scratch buffer the two calls below share for a window of n_events
+ * events.  Its layout depends on the exact n_events, H, W and n_chunks: ask per window.  The caller allocates it (256-byte
+ * aligned, contents arbitrary) and may free it once _fill's launches have run. */
+#define ENERF_EVT_SEGMENT_TILE 4096 /* events of one pixel that are ordered in LDS; longer segments: in global memory */
+int enerf_event_tables_workspace(uint64_t n_events, uint32_t H, uint32_t W, uint32_t n_chunks, uint64_t* bytes);
+/* Pass one over the window.  Per event, its coordinates compared with W, H BEFORE anything is indexed (an event outside
+ * the sensor is skipped and counted): with `tables` != 0 the per-pixel event count and the window position of the pixel's
+ * first event; with n_chunks != 0 the pixel's bit in the bitmap of chunk j, where edges_us[j] <= tt < edges_us[j + 1],
+ * tt = t_ns * 1e-3 (rounded; an event before edges_us[0] or at / after edges_us[n_chunks] is in no chunk).  Then, with
+ * `tables`: the kept pixels (two events or more) ranked by the position of their first event, their counts and the
+ * prefix sum of the counts, left in the workspace for _fill.  With n_chunks: no_event_pixels i64 [n_chunks, H * W] row j
+ * = the linear indices of the pixels WITHOUT an event in chunk j, ascending; the rest of the row is not written.
+ * edges_us f64 [n_chunks + 1] on the device, ascending.  report i64 [4 + n_chunks] on the device: N (events of kept
+ * pixels), P (kept pixels), bad (events outside the sensor), 0, then the n_chunks row lengths; N and P are 0 without
+ * `tables`.  t may be NULL when n_chunks == 0; edges_us / no_event_pixels when n_chunks == 0.  All launches on `stream`;
+ * the host reads `report` after synchronising. */
+int enerf_event_tables_count(const uint16_t* x, const uint16_t* y, const int64_t* t, uint64_t first, uint64_t last,
+                             uint32_t H, uint32_t W, double ns_per_unit, int64_t t_offset, uint32_t tables,
+                             const double* edges_us, uint32_t n_chunks, void* workspace, int64_t* report,
+                             int64_t* no_event_pixels, enerf_stream_t stream);
+/* Pass two, after a _count with `tables` on the same window, workspace and n_chunks, with the N >= 2 and P >= 1 it
+ * reported: the tables build_event_tables returns, in the kernels' layout.  Pixels in the order of their first event, a
+ * pixel's events in stream order (which, the stream being time-sorted and fp32 rounding monotone, is the reference's stable
+ * sort on the fp32 time, ties included).  events f32 [N, 4] rows (x', y', (float) t_ns, +-1) with (x', y') =
+ * rect[y][x][0 .. 1] (rect f32 [H, W, 2]) or, rect == NULL, the integer coordinates as floats; no_successor u8 [N] (last
+ * event of its pixel); num_successor i64 [N] (later events of the pixel); pol_cumsum f64 [N + 1], the exclusive prefix sum
+ * of the polarities (an integer scan, converted: exact); num_at_xy / first_at_xy i64 [P].  events must be 16-byte aligned.
+ * Every output has the same bits on every run.  May be repeated on the same workspace.  An N, P that cannot belong to the
+ * window answers ENERF_E_BADARG; one that merely differs from the report writes nothing out of bounds (rows it cannot
+ * fill are NaN). */
+int enerf_event_tables_fill(const uint16_t* x, const uint16_t* y, const int64_t* t, const int8_t* p, uint64_t first,
+                            uint64_t last, uint32_t H, uint32_t W, const float* rect, double ns_per_unit, int64_t t_offset,
+                            void* workspace, uint32_t n_chunks, uint32_t N, uint32_t P, float* events, uint8_t* no_successor,
+                            int64_t* num_successor, double* pol_cumsum, int64_t* num_at_xy, int64_t* first_at_xy,
+                            enerf_stream_t stream);
+/* The chosen event-free pixels of one chunk through the map (provider.py:1337-1343), one thread per pixel: coords f32
+ * [max(n, 1), 2] row k = rect[pixels[k] / W][pixels[k] % W][0 .. 1], or (pixels[k] % W, pixels[k] / W) with rect == NULL.
+ * n == 0: the one dummy row (0, 0).  A pixels[k] outside [0, H * W) reads nothing: its row is NaN and *bad_index += 1
+ * (bad_index may be NULL). */
+int enerf_no_event_coords(const int64_t* pixels, uint32_t n, const float* rect, uint32_t H, uint32_t W, float* coords,
+                          int32_t* bad_index, enerf_stream_t stream);
 
 /* The event loss of Trainer.train_step_events (nerf/utils.py:499-516, C_thres != -1) and its gradient with respect to
  * the two rendered images, one launch: image1 / image2 [N,3] fp32, pols [N] -> delta [N,1] (use_luma) or [N,3],
