@@ -185,6 +185,10 @@ SIGNATURES = {
     "enerf_debug_error_map_sample_host": [_vp, _vp, _vp, _vp, _u32, _u32, _u32, _vp, _vp],
     "enerf_view_finish": [_vp, _vp, _u32, _u32, _u32, _u32, _u32, _u32, _vp, _vp, _u32, _vp, _vp, _vp, _vp, _vp],
     "enerf_view_minmax": [_vp, _c.c_uint64, _vp, _vp, _vp],
+    "enerf_background_forward": [_vp, _vp, _f32, _u32, _vp, _vp, _u32, _u32, _f32, _u32, _u32, _u32, _vp, _vp, _u32, _u32,
+                                 _vp, _vp, _vp],
+    "enerf_background_backward": [_vp, _vp, _f32, _u32, _vp, _vp, _u32, _u32, _f32, _u32, _u32, _u32, _vp, _vp, _u32, _u32,
+                                  _vp, _vp, _vp, _vp, _vp, _vp],
 }
 
 F32, F16, BF16 = 0, 1, 2

@@ -17,7 +17,7 @@ LIB = os.path.join(LIBDIR, "libenerf_hip.so")
 SOURCES = ["runtime.hip", "raymarching.hip", "gridencoder.hip", "shencoder.hip", "ffmlp.hip", "ffmlp_wgrad.hip",
            "mlp32.hip", "mlp32s.hip", "mlp32s_f16.hip", "nerf_mlp.hip", "nerf_mlp_bwd.hip", "optim.hip", "density_update.hip", "ffnerf.hip", "event_pairs.hip", "train_step.hip",
            "stratified.hip", "mesh.hip", "eval_metrics.hip", "frame_batch.hip", "view_finish.hip",
-           "event_tables.hip"]
+           "event_tables.hip", "background.hip"]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-munsafe-fp-atomics", "-Wall",
          "-Wno-unused-function"]
 # Per-file extras.  ffmlp.hip (forward + dgrad) keeps its MFMA accumulators in arch VGPRs: every accumulator is

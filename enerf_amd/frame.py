@@ -31,9 +31,11 @@ def _channels(model):
     return channels(model)
 
 
-def frame_supported(model, rays_o, perturb, dt_gamma, bg_color):
+def frame_supported(model, rays_o, perturb, dt_gamma, bg_color, background_model=False):
+    """`background_model`: bg_color is the model's own per-ray background (background.py), bg_radius > 0 no refusal."""
     if not (FRAME_ENABLED and raymarching._DEVICE == "cuda" and rays_o.is_cuda and rays_o.dtype == torch.float32
-            and not perturb and dt_gamma == 0 and model.bg_radius <= 0 and not torch.is_grad_enabled()):
+            and not perturb and dt_gamma == 0 and (background_model or model.bg_radius <= 0)
+            and not torch.is_grad_enabled()):
         return False
     C = _channels(model)
     if not 1 <= C <= 3:                              # what the compositing kernels serve

@@ -26,11 +26,13 @@ def channels(model):
     return int(getattr(model, "out_dim_color", 3))
 
 
-def supported(model, rays_o, rays_d, bg_color, dt_gamma):
+def supported(model, rays_o, rays_d, bg_color, dt_gamma, background_model=False):
+    """`background_model`: bg_color is the model's own per-ray background (background.py): bg_radius > 0 is then no
+    refusal, and the tensor may carry a gradient (the node returns d bg)."""
     C = channels(model)
     if not 1 <= C <= 3:                           # the compositing kernels serve 1..3 channels
         return False
-    if not (ENABLED and fnet.ENABLED and model.training and model.cuda_ray and model.bg_radius <= 0
+    if not (ENABLED and fnet.ENABLED and model.training and model.cuda_ray and (background_model or model.bg_radius <= 0)
             and rays_o.is_cuda and rays_o.dtype == torch.float32 and rays_d.dtype == torch.float32
             and not torch.is_autocast_enabled() and not rays_o.requires_grad and not rays_d.requires_grad
             and _rm._DEVICE == "cuda" and torch.is_grad_enabled()):
@@ -38,7 +40,7 @@ def supported(model, rays_o, rays_d, bg_color, dt_gamma):
     if isinstance(bg_color, torch.Tensor):
         # the composite kernels take a scalar, one colour or one colour per ray, fp32 and dense; anything else the reference's
         # `image + (1 - ws)[:, None] * bg_color` would broadcast goes the op-by-op route
-        if (bg_color.requires_grad or not bg_color.is_cuda or bg_color.dtype != torch.float32
+        if ((bg_color.requires_grad and not background_model) or not bg_color.is_cuda or bg_color.dtype != torch.float32
                 or not bg_color.is_contiguous() or bg_color.numel() not in (1, C, C * rays_o.view(-1, 3).shape[0])):
             return False
     probe = rays_o.view(-1, 3)
@@ -239,7 +241,7 @@ class _FusedRenderTrain(Function):
         _rb.composite_rays_train_forward_blend(sigmas, rgb, deltas, rays, M, N, weights_sum, depth, image, bg_color,
                                                out_image)
         out_depth = torch.clamp(depth - nears, min=0) / (fars - nears)
-        if train:
+        if train or (isinstance(bg_color, torch.Tensor) and ctx.needs_input_grad[2]):
             ctx.sv = sv
             ctx.rest = (sigmas, rgb, deltas, rays, weights_sum, image, bg_color, M, N, scale)
         ctx.mark_non_differentiable(out_depth)
@@ -249,6 +251,10 @@ class _FusedRenderTrain(Function):
     def backward(ctx, _g_depth, g_image):
         sigmas, rgb, deltas, rays, weights_sum, image, bg_color, M, N, scale = ctx.rest
         g_image = g_image.reshape(N, rgb.shape[1]).float().contiguous()
+        # ... d/d(bg) = (1 - weights_sum)[:, None] * g: asked for by the background model's per-ray colours only
+        g_bg = ((1 - weights_sum).unsqueeze(-1) * g_image).view_as(bg_color) if ctx.needs_input_grad[2] else None
+        if ctx.sv is None:                       # (no network parameter takes a gradient)
+            return (None, None, g_bg, None) + (None,) * (len(ctx.needs_input_grad) - 4)
         # out_image = image + (1 - weights_sum)[:, None] * bg  ->  d/d(weights_sum) = -(g . bg)
         g_ws = -(g_image * bg_color).sum(-1) if isinstance(bg_color, torch.Tensor) else -(g_image.sum(-1) * bg_color)
         g_ws = g_ws.reshape(N).contiguous()
@@ -257,7 +263,7 @@ class _FusedRenderTrain(Function):
         _rb.composite_rays_train_backward(g_ws, g_image, sigmas, rgb, deltas, rays, weights_sum, image, M, N, g_sigmas,
                                           g_rgbs)
         g = fnet.nerf_backward(ctx.sv, g_sigmas, g_rgbs, sigma_scale=scale)
-        return (None,) * 4 + g
+        return (None, None, g_bg, None) + g
 
 
 def _budget(model):

@@ -7,7 +7,7 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
-from . import fused_mlp, fused_network
+from . import background, fused_mlp, fused_network, raymarching
 from .activation import trunc_exp
 from .encoding import get_encoder
 from .gridencoder import GridEncoder, _supports_layout
@@ -113,6 +113,14 @@ class NeRFNetwork(NeRFRenderer):
     def background(self, x, d):
         h = torch.cat([self._dir_features(d), self.encoder_bg(x)], dim=-1)
         return torch.sigmoid(_run_mlp(self.bg_net, h))
+
+    def background_from_rays(self, rays_o, rays_d, native=None):
+        """rays [N,3] -> background colour [N,out_dim_color]: one native node where background.supported holds, else
+        `background` on the rays' polar coordinates.  `native`: the answer of background.supported for these rays, from a
+        caller that has asked already (a render asks once)."""
+        if background.supported(self, rays_o, rays_d) if native is None else native:
+            return background.background_from_rays(self, rays_o, rays_d)
+        return self.background(raymarching.polar_from_ray(rays_o, rays_d, self.bg_radius), rays_d.reshape(-1, 3))
 
     def color(self, x, d, mask=None, geo_feat=None, **kwargs):
         """Masked colour query (network.py:171-199): rows where mask is False stay zero."""

@@ -11,6 +11,7 @@ The bodies live where the work is done:
     run                  sampler.render_stratified        pure-PyTorch sampler (cuda_ray off; cpu_baseline)
     run_cuda, training   fused_render.render_train        one autograd node per render (MI355X fp32 path)
                          _train_ops                       the four autograd Functions one after the other
+    background           background.background_from_rays  the background model's per-ray colours (bg_radius > 0), one node
     run_cuda, eval       frame.render_frame               every sample marched at once, one compositing pass
                          frame.render_rounds              the reference's round schedule
     update_extra_state   density_update.update / update_torch
@@ -21,7 +22,7 @@ import math
 import torch
 import torch.nn as nn
 
-from . import density_update, frame, fused_render, raymarching, sampler
+from . import background, density_update, frame, fused_render, raymarching, sampler
 
 
 class NeRFRenderer(nn.Module):
@@ -107,17 +108,23 @@ class NeRFRenderer(nn.Module):
                  **kwargs):
         lead = rays_o.shape[:-1]
         rays_o, rays_d = (t.contiguous().view(-1, 3) for t in (rays_o, rays_d))
+        native_bg = False        # the background model through its native node: the fused routes then take its per-ray colours
         if self.bg_radius > 0:
-            bg = self.background(raymarching.polar_from_ray(rays_o, rays_d, self.bg_radius), rays_d)
+            native_bg = hasattr(self, "background_from_rays") and background.supported(self, rays_o, rays_d)
+            if native_bg:
+                bg = self.background_from_rays(rays_o, rays_d, native=True)
+            else:
+                bg = self.background(raymarching.polar_from_ray(rays_o, rays_d, self.bg_radius), rays_d)
         else:
             bg = 1 if bg_color is None else bg_color
         if self.training:
-            if self.bg_radius <= 0 and fused_render.supported(self, rays_o, rays_d, bg, dt_gamma):
+            if (self.bg_radius <= 0 or native_bg) and fused_render.supported(self, rays_o, rays_d, bg, dt_gamma,
+                                                                             background_model=native_bg):
                 depth, image = fused_render.render_train(self, rays_o, rays_d, bg, perturb, force_all_rays, dt_gamma,
                                                          max_steps)
             else:
                 depth, image = self._train_ops(rays_o, rays_d, bg, perturb, force_all_rays, dt_gamma, max_steps)
-        elif frame.frame_supported(self, rays_o, perturb, dt_gamma, bg):
+        elif frame.frame_supported(self, rays_o, perturb, dt_gamma, bg, background_model=native_bg):
             depth, image = frame.render_frame(self, rays_o, rays_d, bg, max_steps)
         else:
             depth, image = frame.render_rounds(self, rays_o, rays_d, bg, perturb, dt_gamma, max_steps)

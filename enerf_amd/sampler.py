@@ -9,12 +9,13 @@ reference-minted fixtures (tests/golden/ref_run_*.npz) and against the native co
     resample_depths      inverse-CDF draw of extra depths where the coarse weights are large
     render_stratified    the whole render: depths -> density -> [resample -> density -> merge] -> colour -> pixel
 
-On the MI355X (CUDA fp32 rays, nerf/network.py nets, upsample_steps = 0, no background model, autocast off)
-render_stratified hands the whole render to stratified.py: the same statement as one native autograd node.
+On the MI355X (CUDA fp32 rays, nerf/network.py nets, upsample_steps = 0, autocast off) render_stratified hands the whole
+render to stratified.py: the same statement as one native autograd node, with the background model's per-ray colours
+(bg_radius > 0) from background.py's node.
 """
 import torch
 
-from . import raymarching, stratified
+from . import background, raymarching, stratified
 
 
 def stratified_depths(nears, fars, n, jitter):
@@ -71,6 +72,14 @@ def render_stratified(model, rays_o, rays_d, num_steps=128, upsample_steps=128, 
     """-> {"depth": [...], "image": [..., out_dim_color]} for rays of any leading shape."""
     if stratified.supported(model, rays_o, rays_d, upsample_steps, bg_color, kwargs.get("out_dim_color")):
         return stratified.render(model, rays_o, rays_d, num_steps, bg_color, perturb)
+    if getattr(model, "bg_radius", -1) > 0 and hasattr(model, "background_from_rays") \
+            and background.supported(model, rays_o, rays_d) \
+            and stratified.supported(model, rays_o, rays_d, upsample_steps, None, kwargs.get("out_dim_color"),
+                                     background_model=True):
+        # the background model in fp32: its per-ray colours from the native node (bg_color is ignored, as below), the
+        # stratified node blends them and hands their gradient back
+        bg = model.background_from_rays(rays_o.contiguous().view(-1, 3), rays_d.contiguous().view(-1, 3), native=True)
+        return stratified.render(model, rays_o, rays_d, num_steps, bg, perturb)
     lead = rays_o.shape[:-1]
     rays_o = rays_o.contiguous().view(-1, 3)
     rays_d = rays_d.contiguous().view(-1, 3)
@@ -105,7 +114,9 @@ def render_stratified(model, rays_o, rays_d, num_steps=128, upsample_steps=128, 
     opacity = w.sum(-1)
     depth = (w * ((z - nears) / (fars - nears)).clamp(0, 1)).sum(-1)
     image = (w.unsqueeze(-1) * rgb).sum(-2)
-    if model.bg_radius > 0:
+    if model.bg_radius > 0 and hasattr(model, "background_from_rays"):
+        bg_color = model.background_from_rays(rays_o, rays_d)
+    elif model.bg_radius > 0:
         bg_color = model.background(raymarching.polar_from_ray(rays_o, rays_d, model.bg_radius), rays_d.reshape(-1, 3))
     elif bg_color is None:
         bg_color = 1

@@ -23,7 +23,10 @@ statement runs, as it does in the reference.
 
 What the PyTorch statement does with host synchronisations (`mask.any()`, boolean indexing) happens here on the device, so
 a forward + backward can be captured in a CUDA graph.  Anything this does not serve -- CPU tensors, autocast, FFMLP nets,
-upsampling, the background model, view directions off, out_dim_color > 3 -- keeps the statement (sampler.py).
+upsampling, view directions off, out_dim_color > 3 -- keeps the statement (sampler.py).  A background model (bg_radius > 0)
+is served in fp32: sampler.render_stratified passes the per-ray colours of background.py's node as bg_color
+(`background_model=True`), and the node here returns their gradient (1 - opacity) g_image; in the fp16 regime and under
+autocast it keeps the statement.
 """
 import numpy as np
 import torch
@@ -44,8 +47,10 @@ KEEP_LAST = False
 last = None
 
 
-def refusals(model, rays_o, rays_d, upsample_steps=0, bg_color=None, out_dim_color=None):
-    """Why this route does not serve the call (empty: it does)."""
+def refusals(model, rays_o, rays_d, upsample_steps=0, bg_color=None, out_dim_color=None, background_model=False):
+    """Why this route does not serve the call (empty: it does).  `background_model`: the caller renders the model's own
+    per-ray background (background.py) and passes it as bg_color: bg_radius > 0 is then no refusal, and the tensor may
+    carry a gradient (the node returns d bg)."""
     why = []
     if not ENABLED:
         why.append("disabled")
@@ -57,8 +62,10 @@ def refusals(model, rays_o, rays_d, upsample_steps=0, bg_color=None, out_dim_col
         why.append("ray gradients")
     if upsample_steps > 0:
         why.append("upsample_steps")
-    if getattr(model, "bg_radius", -1) > 0:
+    if getattr(model, "bg_radius", -1) > 0 and not background_model:
         why.append("bg_radius")
+    if background_model and getattr(model, "__dict__", {}).get("mlp_precision") not in (None, 0):   # (network_cfg's [4])
+        why.append("background model precision")        # (the background's node is fp32: the fp16 / bf16 regimes refuse)
     if torch.is_autocast_enabled():
         why.append("autocast")
     if getattr(model, "disable_view_direction", True):
@@ -70,21 +77,21 @@ def refusals(model, rays_o, rays_d, upsample_steps=0, bg_color=None, out_dim_col
         why.append("network")
     elif not _ge._supports_layout():
         why.append("grid backend")
-    if _background_form(bg_color, rays_o, c) is None:
+    if _background_form(bg_color, rays_o, c, background_model) is None:
         why.append("bg_color")
     return why
 
 
-def supported(model, rays_o, rays_d, upsample_steps=0, bg_color=None, out_dim_color=None):
-    return not refusals(model, rays_o, rays_d, upsample_steps, bg_color, out_dim_color)
+def supported(model, rays_o, rays_d, upsample_steps=0, bg_color=None, out_dim_color=None, background_model=False):
+    return not refusals(model, rays_o, rays_d, upsample_steps, bg_color, out_dim_color, background_model)
 
 
-def _background_form(bg, rays_o, C):
+def _background_form(bg, rays_o, C, may_need_grad=False):
     """"const": None or a number; "shared": a tensor of C values; "per_ray": one row of C per ray; None: anything else."""
     if bg is None or isinstance(bg, (int, float)):
         return "const"
-    if not isinstance(bg, torch.Tensor) or bg.dtype != torch.float32 or bg.requires_grad or bg.dim() < 1 \
-            or bg.shape[-1] != C or bg.device != rays_o.device:
+    if not isinstance(bg, torch.Tensor) or bg.dtype != torch.float32 or (bg.requires_grad and not may_need_grad) \
+            or bg.dim() < 1 or bg.shape[-1] != C or bg.device != rays_o.device:
         return None
     n = rays_o.numel() // 3
     if bg.numel() == C:
@@ -96,7 +103,7 @@ def _background_form(bg, rays_o, C):
 
 def _background(bg, rays_o, N, C):
     """-> (bg as a contiguous [C] or [N, C] fp32 tensor, per_ray flag)"""
-    form = _background_form(bg, rays_o, C)
+    form = _background_form(bg, rays_o, C, True)
     if form == "const":
         return torch.full((C,), 1.0 if bg is None else float(bg), dtype=torch.float32, device=rays_o.device), 0
     if form == "shared":
@@ -116,7 +123,7 @@ def render(model, rays_o, rays_d, num_steps, bg_color=None, perturb=False):
     u = torch.rand((N, T), device=dev) if perturb else None
     bg, per_ray = _background(bg_color, rays_o, N, C)
     params = _fn.network_params(model)
-    train = torch.is_grad_enabled() and any(p.requires_grad for p in params)
+    train = torch.is_grad_enabled() and (any(p.requires_grad for p in params) or bg.requires_grad)
     cfg = _fn.network_cfg(model)
     geo = dict(T=T, C=C, min_near=float(model.min_near), density_scale=float(model.density_scale), cfg=cfg)
     image, depth = _StratifiedRender.apply(ro, rd, u, bg, per_ray, aabb, geo, train, params[0],
@@ -213,7 +220,7 @@ def render_forward(ro, rd, u, bg, per_ray, aabb, geo, train, embeddings, offsets
     if not train:
         return image, depth, None
     sv = dict(rd=rd, bg=bg, per_ray=per_ray, N=N, T=T, C=C, B=B, cap=cap, inv_T=inv_T, s_dens=s_dens, z=z, xyz=xyz,
-              nears=nears, fars=fars, sigma=sigma, h16=h16, feats=feats, fb_s=fb_s, w=w, count=count, incl=incl, cin=cin,
+              nears=nears, fars=fars, opacity=opacity, sigma=sigma, h16=h16, feats=feats, fb_s=fb_s, w=w, count=count, incl=incl, cin=cin,
               rgb=rgb, fb_c=fb_c, seg_s=seg_s, seg_c=seg_c, weights=weights, emb=emb, offsets=offsets, param=embeddings,
               S=S, H=base_resolution, gridtype=gridtype, affine=affine, prec=prec, store=store, cdt=cdt)
     return image, depth, sv
@@ -288,5 +295,9 @@ class _StratifiedRender(Function):
     def backward(ctx, g_image, g_depth):
         sv = ctx.sv
         ctx.sv = None
+        g_bg = None
+        if ctx.needs_input_grad[3] and g_image is not None:
+            # image = sum w rgb + (1 - opacity) bg: asked for by the background model's per-ray colours only
+            g_bg = (1 - sv["opacity"]).unsqueeze(-1) * g_image.float().reshape(sv["N"], sv["C"])
         g = render_backward(sv, g_image, g_depth)
-        return (None,) * 8 + (g[0], None) + tuple(g[1:])
+        return (None,) * 3 + (g_bg,) + (None,) * 4 + (g[0], None) + tuple(g[1:])

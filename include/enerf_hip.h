@@ -77,7 +77,9 @@ const char* enerf_last_error(void);
  *     Still 13: enerf_event_c_estimate added (the implicit contrast threshold's four medians) -- a new
  *     symbol, nothing existing changed.
  *     Still 13: enerf_event_tables_workspace / _count / _fill and enerf_no_event_coords added (a raw event stream to the
- *     pair kernels' tables) -- new symbols, nothing existing changed. */
+ *     pair kernels' tables) -- new symbols, nothing existing changed.
+ *     Still 13: enerf_background_forward / _backward added (the background model in one launch each way, DESIGN.md
+ *     4.21) -- new symbols, nothing existing changed. */
 #define ENERF_ABI_VERSION 13
 int enerf_abi_version(void);
 /* The library keeps grow-only scratch buffers per device (march chunk log, grid-backward record lists, ...).  Growing one
@@ -1221,6 +1223,29 @@ int enerf_view_finish(const float* image, const float* depth, uint32_t h, uint32
                       uint32_t flags, const float* minmax, float* accum, uint32_t spp, float* out_f32, uint8_t* out_u8,
                       float* depth_f32, uint8_t* depth_u8, enerf_stream_t stream);
 int enerf_view_minmax(const float* image, uint64_t n, float* ws, float* minmax, enerf_stream_t stream);
+
+/* ------------------------------------------------------------------ background model (bg_radius > 0)
+ * nerf/network.py `background` behind raymarching.polar_from_ray, csrc/background.hip; DESIGN.md 4.21.  Per ray:
+ *   p = enerf_polar_from_ray's pair (the same arithmetic);  grid = the D = 2, level_dim 2 encoder of (p + 1) / 2 over
+ *   `embeddings` [offsets[L], 2] fp32, level geometry (offsets [L + 1] on the device, S, H, gridtype) as
+ *   enerf_grid_encode_forward takes it;  sh = the 16 values of enerf_sh_encode_forward(degree 4) of rays_d, or zeros when
+ *   use_dirs == 0;  bg = sigmoid(W1 relu(W0 [sh | grid])), w0 [64, 16 + 2L] and w1 [C, 64] row-major as nn.Linear.weight.
+ * forward: ONE launch, bg [N, C].  trace (NULL in production) receives [N, 2 + 16 + 2L]: p and the MLP's input row.
+ * backward: one launch plus one small reduce over its workgroups' sums.  g_bg = (1 - weights_sum[n]) * grad_image
+ *   [N, C] (weights_sum NULL: the factor is 1); the forward is recomputed from the rays.  grad_w0 [64, 16 + 2L] and grad_w1
+ *   [C, 64] are WRITTEN, summed in a fixed order (the same bits on every run); grad_embeddings [offsets[L], 2] is ADDED
+ *   into with float atomics (the caller zero-fills it; its last bits depend on arrival order).
+ * Both: C outside 1..3, hidden != 64, level_dim != 2, L outside 1..8 or a NULL pointer other than trace / weights_sum
+ * answer ENERF_E_BADARG and write nothing; N == 0 returns 0 and touches nothing. */
+int enerf_background_forward(const float* rays_o, const float* rays_d, float radius, uint32_t N, const float* embeddings,
+                             const int32_t* offsets, uint32_t L, uint32_t level_dim, float S, uint32_t H, uint32_t gridtype,
+                             uint32_t use_dirs, const float* w0, const float* w1, uint32_t hidden, uint32_t C, float* bg,
+                             float* trace, enerf_stream_t stream);
+int enerf_background_backward(const float* rays_o, const float* rays_d, float radius, uint32_t N, const float* embeddings,
+                              const int32_t* offsets, uint32_t L, uint32_t level_dim, float S, uint32_t H,
+                              uint32_t gridtype, uint32_t use_dirs, const float* w0, const float* w1, uint32_t hidden,
+                              uint32_t C, const float* grad_image, const float* weights_sum, float* grad_w0, float* grad_w1,
+                              float* grad_embeddings, enerf_stream_t stream);
 
 #ifdef __cplusplus
 }
