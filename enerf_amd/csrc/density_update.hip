@@ -12,8 +12,11 @@
 //
 // What the reference does with ~40 torch ops per cascade, three host synchronisations (nonzero, two .item()) and 1 M-point
 // scattered gathers is here ~10 launches, one read-back of 16 bytes, and coherent gathers: the sampled cells are sorted
-// (23-bit radix sort of (cascade, Morton index) keys) so neighbouring query points share hash-grid rows.  The sampling
-// is the same in distribution, not in its random numbers (torch's Philox stream is not reproduced): parity unpinned.
+// (a bucket sort by value of the (cascade, Morton index) keys, up to 26 bits: see k_sort_count below) so neighbouring
+// query points share hash-grid rows.  The sampling is the same in distribution as the reference's, not in its random
+// numbers (torch's Philox stream is not reproduced).  It is a pure function of (grid, C, H, bound, n_uniform, seed):
+// keys, occupied list, sorted order and jittered positions are pinned, indices element for element and positions bit
+// for bit, to the numpy statement tests/density_cells_ref.py by tests/test_gpu_density_cells_exact.py.
 
 #include "common.h"
 #include "sweep_points.h"
@@ -439,8 +442,7 @@ int enerf_density_grid_cells(const float* density_grid, uint32_t C, uint32_t H, 
     const uint32_t P = C * 2 * n_uniform;
     const uint32_t blocks_per_cas = H3 / kOccBlock, nblocks = C * blocks_per_cas;
     // the sort's geometry: buckets of 2^low consecutive key values, at most kSortMaxBuckets of them
-    uint32_t key_bits = bits + log2u(C);
-    if ((1u << log2u(C)) < C) key_bits++;                                   // (C not a power of two)
+    const uint32_t key_bits = bits + log2u(C);                              // (log2u rounds up: 2 bits for C = 3, 3 for C = 5)
     const uint32_t low = key_bits > 24 ? key_bits - 12 : 12;
     if (low > kSortMaxLow)
         ENERF_BADARG("density_grid_cells: the partial update sorts keys of up to 26 bits (C * H^3 <= 2^26 cells), got %u bits", key_bits);

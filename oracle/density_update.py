@@ -14,7 +14,8 @@ over this oracle (oracle/make_golden.py gold_cuda_ray -> tests/golden/ref_cuda_r
 route (density_update.update_torch / mark_untrained_torch) bit for bit on the same torch random stream
 (tests/test_host_cuda_ray_vs_reference.py); the device-side passes are compared with that route and with these functions
 on the GPU (tests/test_gpu_density_update.py): which cells a device-side update draws comes from its own counter-based
-generator and is checked in distribution.
+generator and is checked in distribution there, and exactly against its own host statement (tests/density_cells_ref.py)
+in tests/test_gpu_density_cells_exact.py.
 """
 import numpy as np
 
