@@ -123,6 +123,7 @@ SIGNATURES = {
     "enerf_event_tables_fill": [_vp, _vp, _vp, _vp, _c.c_uint64, _c.c_uint64, _u32, _u32, _vp, _c.c_double, _c.c_int64,
                                 _vp, _u32, _u32, _u32, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
     "enerf_no_event_coords": [_vp, _u32, _vp, _u32, _u32, _vp, _vp, _vp],
+    "enerf_debug_event_segment_sort": [_vp, _u32, _vp, _vp, _u32, _vp, _vp],
     "enerf_occupied_box_update":[_vp, _u32, _u32, _f32, _vp],
     "enerf_debug_mlp32_fused_backward": [_int],
     "enerf_mlp32_precision": [_int],

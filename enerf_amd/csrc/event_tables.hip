@@ -566,6 +566,26 @@ int enerf_event_tables_fill(const uint16_t* x, const uint16_t* y, const int64_t*
     return scan(fin, N, nullptr, ws.sums, ws.ctr + C_POL, s, "event_tables_fill: finish");
 }
 
+// testing aid: the two sort launches of enerf_event_tables_fill on segments of the caller's choice
+int enerf_debug_event_segment_sort(uint32_t* idx, uint32_t N, const uint32_t* num, const uint32_t* first, uint32_t P,
+                                   void* workspace, enerf_stream_t stream) {
+    if (!idx || !num || !first || !workspace) ENERF_BADARG("debug_event_segment_sort: null pointer");
+    if (((uintptr_t)workspace & 7) != 0) ENERF_BADARG("debug_event_segment_sort: the workspace must be 8-byte aligned");
+    if (N < 1 || N > kMaxEvents || P < 1 || P > N) ENERF_BADARG("debug_event_segment_sort: N = %u, P = %u", N, P);
+    int64_t* num_at_xy = (int64_t*)workspace;          // [P], [P], then the list of long segments [P] and the counters
+    int64_t* first_at_xy = num_at_xy + P;
+    uint32_t* big = (uint32_t*)(first_at_xy + P);
+    uint32_t* ctr = big + P;
+    hipStream_t s = (hipStream_t)stream;
+    k_clear<<<1, kThreads, 0, s>>>(nullptr, 0, ctr);
+    ENERF_LAUNCH_CHECK("debug_event_segment_sort: clear");
+    k_sort_small<<<div_up(P, kThreads), kThreads, 0, s>>>(num, first, idx, N, P, big, ctr, num_at_xy, first_at_xy);
+    ENERF_LAUNCH_CHECK("debug_event_segment_sort: sort");
+    k_sort_big<<<P < kSortBlocks ? P : kSortBlocks, kThreads, 0, s>>>(num, first, idx, N, P, big, ctr);
+    ENERF_LAUNCH_CHECK("debug_event_segment_sort: segment sort");
+    return 0;
+}
+
 int enerf_no_event_coords(const int64_t* pixels, uint32_t n, const float* rect, uint32_t H, uint32_t W, float* coords,
                           int32_t* bad_index, enerf_stream_t stream) {
     if (H == 0 || W == 0 || (uint64_t)H * W > kMaxPixels) ENERF_BADARG("no_event_coords: a %u x %u sensor", H, W);

@@ -79,7 +79,9 @@ const char* enerf_last_error(void);
  *     Still 13: enerf_event_tables_workspace / _count / _fill and enerf_no_event_coords added (a raw event stream to the
  *     pair kernels' tables) -- new symbols, nothing existing changed.
  *     Still 13: enerf_background_forward / _backward added (the background model in one launch each way, DESIGN.md
- *     4.21) -- new symbols, nothing existing changed. */
+ *     4.21) -- new symbols, nothing existing changed.
+ *     Still 13: enerf_debug_event_segment_sort added (a testing aid: the segment sorts of enerf_event_tables_fill on
+ *     segments of the caller's choice) -- a new symbol, nothing existing changed. */
 #define ENERF_ABI_VERSION 13
 int enerf_abi_version(void);
 /* The library keeps grow-only scratch buffers per device (march chunk log, grid-backward record lists, ...).  Growing one
@@ -778,6 +780,15 @@ int enerf_event_tables_fill(const uint16_t* x, const uint16_t* y, const int64_t*
  * (bad_index may be NULL). */
 int enerf_no_event_coords(const int64_t* pixels, uint32_t n, const float* rect, uint32_t H, uint32_t W, float* coords,
                           int32_t* bad_index, enerf_stream_t stream);
+/* Testing aid: the two sort launches of enerf_event_tables_fill (a thread per segment of at most 32 entries, a workgroup
+ * per longer one, on the grid _fill uses for P segments) on segments of the caller's choice, so that a test decides what
+ * the sort is handed -- in _fill it only ever sees the nearly ascending arrival order of the placement's atomics.
+ * idx u32 [N] on the device; segment r is idx[first[r] .. first[r] + num[r]) (num, first u32 [P], 1 <= P <= N) and comes
+ * back ascending; a segment that does not lie inside [0, N) is left alone, and so is every entry outside the segments.
+ * workspace: 20 * P + 32 bytes on the device, 8-byte aligned, contents arbitrary; afterwards it begins with num and first
+ * as i64 [P] each (the num_at_xy / first_at_xy of _fill). */
+int enerf_debug_event_segment_sort(uint32_t* idx, uint32_t N, const uint32_t* num, const uint32_t* first, uint32_t P,
+                                   void* workspace, enerf_stream_t stream);
 
 /* The event loss of Trainer.train_step_events (nerf/utils.py:499-516, C_thres != -1) and its gradient with respect to
  * the two rendered images, one launch: image1 / image2 [N,3] fp32, pols [N] -> delta [N,1] (use_luma) or [N,3],

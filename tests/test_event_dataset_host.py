@@ -129,7 +129,8 @@ def test_new_entry_points_are_declared_bound_and_the_header_stays_at_13():
     from enerf_amd import _lib as L
     from enerf_amd import build as B
     from enerf_amd import event_dataset as D
-    names = ["enerf_event_tables_workspace", "enerf_event_tables_count", "enerf_event_tables_fill", "enerf_no_event_coords"]
+    names = ["enerf_event_tables_workspace", "enerf_event_tables_count", "enerf_event_tables_fill", "enerf_no_event_coords",
+             "enerf_debug_event_segment_sort"]
     with open(L.HEADER_PATH) as f:
         header = f.read()
     assert L.header_abi_version() == 13 and "event_tables.hip" in B.SOURCES
