@@ -124,6 +124,12 @@ SIGNATURES = {
                                 _vp, _u32, _u32, _u32, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
     "enerf_no_event_coords": [_vp, _u32, _vp, _u32, _u32, _vp, _vp, _vp],
     "enerf_debug_event_segment_sort": [_vp, _u32, _vp, _vp, _u32, _vp, _vp],
+    "enerf_event_pixel_stats": [_vp, _vp, _vp, _c.c_uint64, _c.c_uint64, _u32, _u32, _vp, _vp, _vp, _vp, _vp, _vp],
+    "enerf_event_accumulation_image": [_vp, _vp, _c.c_uint64, _c.c_uint64, _u32, _u32, _vp, _vp],
+    "enerf_event_count_moments": [_vp, _u32, _u32, _vp, _vp],
+    "enerf_event_hot_mask": [_vp, _u32, _u32, _c.c_uint64, _vp, _vp, _vp],
+    "enerf_event_stream_compact_workspace": [_c.c_uint64, _c.POINTER(_c.c_uint64)],
+    "enerf_event_stream_compact": [_vp, _vp, _vp, _vp, _c.c_uint64, _u32, _u32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
     "enerf_occupied_box_update":[_vp, _u32, _u32, _f32, _vp],
     "enerf_debug_mlp32_fused_backward": [_int],
     "enerf_mlp32_precision": [_int],

@@ -17,7 +17,7 @@ LIB = os.path.join(LIBDIR, "libenerf_hip.so")
 SOURCES = ["runtime.hip", "raymarching.hip", "gridencoder.hip", "shencoder.hip", "ffmlp.hip", "ffmlp_wgrad.hip",
            "mlp32.hip", "mlp32s.hip", "mlp32s_f16.hip", "nerf_mlp.hip", "nerf_mlp_bwd.hip", "optim.hip", "density_update.hip", "ffnerf.hip", "event_pairs.hip", "train_step.hip",
            "stratified.hip", "mesh.hip", "eval_metrics.hip", "frame_batch.hip", "view_finish.hip",
-           "event_tables.hip", "background.hip"]
+           "event_tables.hip", "background.hip", "event_stats.hip"]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-munsafe-fp-atomics", "-Wall",
          "-Wno-unused-function"]
 # Per-file extras.  ffmlp.hip (forward + dgrad) keeps its MFMA accumulators in arch VGPRs: every accumulator is
@@ -32,7 +32,7 @@ EXTRA = {"ffmlp.hip": _VGPR_FORM, "mlp32s.hip": _VGPR_FORM, "mlp32s_f16.hip": _V
 FLAGS += os.environ.get("ENERF_DEFINES", "").split()
 HEADERS = [os.path.join(CSRC, "common.h"), os.path.join(CSRC, "ffmlp_common.h"), os.path.join(CSRC, "mlp32_common.h"), os.path.join(CSRC, "mlp32s_ops.h"), os.path.join(CSRC, "mfma_guard.h"),
            os.path.join(CSRC, "sh_basis.h"), os.path.join(CSRC, "march_lattice.h"), os.path.join(CSRC, "sweep_points.h"),
-           os.path.join(CSRC, "mc_tables.h"), os.path.join(CSRC, "pose_track.h"),
+           os.path.join(CSRC, "mc_tables.h"), os.path.join(CSRC, "pose_track.h"), os.path.join(CSRC, "event_scan.h"),
            os.path.join(_HERE, "..", "include", "enerf_hip.h")]
 
 

@@ -12,7 +12,10 @@ not fire (provider.py:1283-1351).  Here that is one object:
                               the dicts of event_sampler.build_event_tables / build_no_event_tables, built by
                               csrc/event_tables.hip on device tensors and by the torch statements
                               below on CPU tensors
-  EventSampler.from_stream    (event_sampler.py) every frame's tables from a stream, then the sampler
+                  .pixel_counts / .accumulation_image / .hot_pixels / .without_pixels
+                              per-pixel counts, render_ev_accumulation's pictures (utils/plot_utils.py), a hot-pixel mask
+                              and the stream without it, by csrc/event_stats.hip
+  EventSampler.from_stream   (event_sampler.py) every frame's tables from a stream, then the sampler
 
 Pixels are keyed on the SENSOR pixel y * W + x, which is what the reference's float key amounts to for an injective map:
 `build_event_tables` keys on the truncated coordinates and merges the sensor pixels that a compressing map truncates into
@@ -115,6 +118,18 @@ def chunk_edges(start_us, end_us, chunk_len_ms=20.0):
     return edges, dt_us
 
 
+_MAX_EVENTS = 1 << 30      # events of one call (kMaxEvents of csrc/event_tables.hip and csrc/event_stats.hip)
+
+
+def _hot_threshold(n, S, Q, n_sigma, max_count):
+    """EventStream.hot_pixels' integer threshold from the counts' exact moments, in Python floats."""
+    if max_count is not None:
+        return int(max_count)
+    mu = S / n
+    sigma = math.sqrt(max(Q / n - mu * mu, 0.0))
+    return int(math.floor(mu + float(n_sigma) * sigma))
+
+
 class EventStream:
     """A raw event stream with its sensor: x, y (sensor pixel), t (ascending, `unit_per_ms` units per millisecond), p
     (polarity), all [E] on one device; the sensor's H, W; `rectify_map` [H, W, 2] (x', y') or None for the identity
@@ -123,7 +138,11 @@ class EventStream:
 
     On device tensors .tables / .no_event_tables / .batch_tables run csrc/event_tables.hip (there is no fallback: a
     missing library raises); on CPU tensors they run tables_statement and build_no_event_tables on the sensor
-    coordinates.  After each of them `last_report` holds {"N", "P", "bad"} of the window."""
+    coordinates.  After each of them `last_report` holds {"N", "P", "bad"} of the window.
+
+    The loader's side works the same way (csrc/event_stats.hip on device tensors, torch statements on CPU tensors, DESIGN.md
+    4.22): .pixel_counts, .accumulation_image (the reference's loaded_events_undist_viz pictures), .hot_pixels and
+    .without_pixels; each fills `last_report` as its docstring says."""
 
     def __init__(self, x, y, t, p, H, W, rectify_map=None, unit_per_ms=1000, t_offset=0, ms_to_idx=None):
         t = torch.as_tensor(t)
@@ -187,6 +206,177 @@ class EventStream:
     def batch_tables(self, first, last, start_us, end_us, chunk_len_ms=20.0, generator=None, keep=None):
         """(tables, no_event_tables) from ONE pass over the window: the chunks' hit bitmaps ride in the count pass."""
         return self._build(first, last, True, (start_us, end_us, chunk_len_ms, generator, keep))
+
+    # ---- the loader's side: counts, pictures, hot pixels (DESIGN.md 4.22) ---------------------------------------------
+    def pixel_counts(self, first, last):
+        """int32 [H, W, 2]: the events of the window [first, last) per sensor pixel, [..., 0] those of polarity -1,
+        [..., 1] those of polarity +1.  last_report = {"events", "bad"}."""
+        first, last = self._span(first, last)
+        counts = self._stats(first, last, False, False)[0]
+        self.last_report = {"events": last - first, "bad": 0}
+        return counts
+
+    def accumulation_image(self, first, last, rectified=False):
+        """uint8 [H, W, 3]: what utils/plot_utils.py render_ev_accumulation returns for the window (provider.py:227-230,
+        :313-316).  White; then, in stream order, every event paints its cell with its polarity, a later event over an
+        earlier one: -1 (255, 0, 0), +1 (0, 0, 255).  The cell is the sensor pixel (y, x) or, `rectified`,
+        (int(yr), int(xr)) of (xr, yr) = rectify_map[y, x] for the events with xr >= 0, yr >= 0, xr < W, yr < H in
+        float32 (a NaN fails).  last_report = {"events", "bad"}."""
+        first, last = self._span(first, last)
+        if rectified and self.rectify_map is None:
+            raise ValueError("EventStream.accumulation_image: rectified=True needs a rectify_map")
+        _, last_event = self._stats(first, last, not rectified, bool(rectified))
+        if self.device.type == "cuda":
+            from . import _lib as L
+            img = torch.empty(self.H, self.W, 3, dtype=torch.uint8, device=self.device)
+            with torch.cuda.device(self.device):
+                L.check(L.lib().enerf_event_accumulation_image(last_event.data_ptr(), self.p.data_ptr(), first, last, self.H,
+                                                               self.W, img.data_ptr(), L.stream_handle()),
+                        "event_accumulation_image")
+        else:
+            pol = self.p[first:last][(last_event - 1).clamp(min=0)]
+            img = torch.full((self.H * self.W, 3), 255, dtype=torch.uint8)
+            img[(last_event > 0) & (pol < 0)] = torch.tensor([255, 0, 0], dtype=torch.uint8)
+            img[(last_event > 0) & (pol > 0)] = torch.tensor([0, 0, 255], dtype=torch.uint8)
+            img = img.view(self.H, self.W, 3)
+        self.last_report = {"events": last - first, "bad": 0}
+        return img
+
+    def hot_pixels(self, first=0, last=None, *, n_sigma=None, max_count=None):
+        """bool [H, W]: the sensor pixels with more events in the window than a threshold T.  c = events per pixel (both
+        polarities); over the n pixels with c > 0, S = sum c and Q = sum c * c (exact integers).  `max_count`: T =
+        max_count.  `n_sigma`: T = floor(mu + n_sigma * sigma) with mu = S / n, sigma = sqrt(max(Q / n - mu * mu, 0)), in
+        Python floats on the host -- an integer from exact integers, so both routes give the same mask.  Exactly one of
+        the two; there is no default (the reference defines no filter).
+        last_report = {"active": n, "events": S, "threshold": T, "hot", "hot_events"}."""
+        if (n_sigma is None) == (max_count is None):
+            raise ValueError("EventStream.hot_pixels: exactly one of n_sigma and max_count")
+        if n_sigma is not None and not (math.isfinite(float(n_sigma)) and float(n_sigma) >= 0.0):
+            raise ValueError(f"EventStream.hot_pixels: n_sigma = {n_sigma} (finite, >= 0)")
+        if max_count is not None and (int(max_count) != max_count or int(max_count) < 0):
+            raise ValueError(f"EventStream.hot_pixels: max_count = {max_count} (an integer >= 0)")
+        first, last = self._span(first, len(self) if last is None else last)
+        H, W, dev = self.H, self.W, self.device
+        if dev.type == "cuda":
+            from . import _lib as L
+            lib = L.lib()
+            with torch.cuda.device(dev):
+                words = torch.empty(6, dtype=torch.int64, device=dev)          # n, S, Q, bad | hot, hot_events
+                counts = self._stats_launch(first, last, False, False, words[3:4])[0]
+                stream = L.stream_handle()
+                L.check(lib.enerf_event_count_moments(counts.data_ptr(), H, W, words.data_ptr(), stream),
+                        "event_count_moments")
+                n, S, Q, bad = (int(v) for v in words[:4].tolist())            # the read-back before the mask
+                self._sensor(bad)
+                T = _hot_threshold(n, S, Q, n_sigma, max_count)
+                mask = torch.empty(H, W, dtype=torch.uint8, device=dev)
+                L.check(lib.enerf_event_hot_mask(counts.data_ptr(), H, W, min(T, 1 << 62), mask.data_ptr(),
+                                                 words[4:].data_ptr(), stream), "event_hot_mask")
+                hot, hot_events = (int(v) for v in words[4:].tolist())         # ... and the one after
+            mask = mask.view(torch.bool)
+        else:
+            c = self._stats(first, last, False, False)[0].to(torch.int64).sum(-1)
+            n, S, Q = int((c > 0).sum()), int(c.sum()), int((c * c).sum())
+            T = _hot_threshold(n, S, Q, n_sigma, max_count)
+            mask = c > min(T, 1 << 62)
+            hot, hot_events = int(mask.sum()), int(c[mask].sum())
+        self.last_report = {"active": n, "events": S, "threshold": T, "hot": hot, "hot_events": hot_events}
+        return mask
+
+    def without_pixels(self, mask):
+        """A new EventStream without the events at the sensor pixels where `mask` (bool [H, W], on the stream's device) is
+        set; the others keep their order.  H, W, the map, unit_per_ms and t_offset are carried over; the millisecond index
+        is rebuilt.  A mask that leaves no event raises (a stream is never empty).  On the source stream last_report =
+        {"kept", "removed"}."""
+        if not torch.is_tensor(mask) or mask.dtype != torch.bool or tuple(mask.shape) != (self.H, self.W):
+            raise ValueError(f"EventStream.without_pixels: the mask must be a bool tensor of shape ({self.H}, {self.W})")
+        if mask.device != self.x.device:
+            raise ValueError(f"EventStream.without_pixels: the mask is on {mask.device}, the stream on {self.x.device}")
+        E = len(self)
+        if E > _MAX_EVENTS:
+            raise ValueError(f"EventStream.without_pixels: {E} events (at most 2^30 in one call)")
+        mask = mask.contiguous()
+        if self.device.type == "cuda":
+            from . import _lib as L
+            lib, dev = L.lib(), self.device
+            with torch.cuda.device(dev):
+                nbytes = ctypes.c_uint64(0)
+                L.check(lib.enerf_event_stream_compact_workspace(E, ctypes.byref(nbytes)), "event_stream_compact_workspace")
+                ws = torch.empty(nbytes.value, dtype=torch.uint8, device=dev)
+                out = [torch.empty_like(v) for v in (self.x, self.y, self.t, self.p)]
+                report = torch.empty(2, dtype=torch.int32, device=dev)
+                L.check(lib.enerf_event_stream_compact(
+                    self.x.data_ptr(), self.y.data_ptr(), self.t.data_ptr(), self.p.data_ptr(), E, self.H, self.W,
+                    mask.view(torch.uint8).data_ptr(), ws.data_ptr(), *(v.data_ptr() for v in out), report.data_ptr(),
+                    L.stream_handle()), "event_stream_compact")
+                kept, bad = report.tolist()                                    # the one read-back: sizes the result
+            self._sensor(bad)
+            cols = [v[:kept].clone() for v in out] if 0 < kept < E else out
+        else:
+            xs, ys = self.x.to(torch.int64), self.y.to(torch.int64)
+            self._sensor(int(((xs >= self.W) | (ys >= self.H)).sum()))
+            keep = ~mask[ys, xs]
+            kept = int(keep.sum())
+            cols = [v[keep] for v in (self.x, self.y, self.t, self.p)]
+        self.last_report = {"kept": kept, "removed": E - kept}
+        if kept == 0:
+            raise ValueError("EventStream.without_pixels: the mask removes every event")
+        return EventStream(*cols, self.H, self.W, self.rectify_map, self.unit_per_ms, self.t_offset, None)
+
+    def _span(self, first, last):
+        first, last = int(first), int(last)
+        if not 0 <= first <= last <= len(self):
+            raise ValueError(f"EventStream: window [{first}, {last}) of a stream of {len(self)} events")
+        if first == last:
+            raise ValueError("EventStream: an empty window")
+        if last - first > _MAX_EVENTS:
+            raise ValueError(f"EventStream: a window of {last - first} events (at most 2^30 in one call)")
+        return first, last
+
+    def _sensor(self, bad):
+        if bad > 0:
+            self.last_report = {"bad": bad}
+            raise ValueError(f"EventStream: {bad} event(s) outside the {self.W} x {self.H} sensor")
+
+    def _stats_launch(self, first, last, want_sensor, want_rect, bad):
+        """enerf_event_pixel_stats on the window -> (counts [H, W, 2] int32, the last-event array asked for, int32 [H * W]
+        with 0 for no event, or None); `bad`: one int64 word on the device that takes the out-of-sensor count."""
+        from . import _lib as L
+        H, W, dev = self.H, self.W, self.device
+        counts = torch.empty(H, W, 2, dtype=torch.int32, device=dev)
+        last_event = torch.empty(H * W, dtype=torch.int32, device=dev) if want_sensor or want_rect else None
+        L.check(L.lib().enerf_event_pixel_stats(
+            self.x.data_ptr(), self.y.data_ptr(), self.p.data_ptr(), first, last, H, W,
+            self.rectify_map.data_ptr() if want_rect else None, counts.data_ptr(),
+            last_event.data_ptr() if want_sensor else None, last_event.data_ptr() if want_rect else None, bad.data_ptr(),
+            L.stream_handle()), "event_pixel_stats")
+        return counts, last_event
+
+    def _stats(self, first, last, want_sensor, want_rect):
+        """(counts, last-event array) of the window on either route, the sensor check made (one read-back on the device)."""
+        H, W = self.H, self.W
+        if self.device.type == "cuda":
+            with torch.cuda.device(self.device):
+                bad = torch.empty(1, dtype=torch.int64, device=self.device)
+                out = self._stats_launch(first, last, want_sensor, want_rect, bad)
+                self._sensor(int(bad))
+            return out
+        xs, ys = self.x[first:last].to(torch.int64), self.y[first:last].to(torch.int64)
+        self._sensor(int(((xs >= W) | (ys >= H)).sum()))
+        pix = ys * W + xs
+        counts = torch.bincount(2 * pix + (self.p[first:last] > 0), minlength=2 * H * W).view(H, W, 2).to(torch.int32)
+        last_event = None
+        if want_sensor or want_rect:
+            number = torch.arange(1, last - first + 1, dtype=torch.int64)
+            cell = pix
+            if want_rect:
+                r = self.rectify_map[ys, xs]
+                xr, yr = r[:, 0], r[:, 1]
+                ok = (xr >= 0) & (yr >= 0) & (xr < W) & (yr < H)
+                cell = yr[ok].to(torch.int64) * W + xr[ok].to(torch.int64)
+                number = number[ok]
+            last_event = torch.zeros(H * W, dtype=torch.int64).scatter_reduce(0, cell, number, "amax")
+        return counts, last_event
 
     # ---- both routes --------------------------------------------------------------------------------------------------
     def _build(self, first, last, want_tables, no_ev):

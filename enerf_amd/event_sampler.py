@@ -410,15 +410,29 @@ class EventSampler:
 
     @classmethod
     def from_stream(cls, stream, centres_us, track, intrinsics_evs, batch_size_evs, accumulate_evs=0, acc_max_num_evs=0,
-                    negative_event_sampling=0, shrink_us=0, frames=None, seed=None):
+                    negative_event_sampling=0, shrink_us=0, frames=None, seed=None, viz_dir=None, viz_names=None):
         """The sampler of a raw stream (event_dataset.EventStream), as EventNeRFDataset.__init__ and
         load_events_at_frame_idxs prepare it (provider.py:1107-1362): frame i takes the events of
         [centres_us[i] + shrink_us, centres_us[i + 1] - shrink_us) (event_dataset.event_centres) and, with
         `negative_event_sampling`, the no-event tables of the unshrunk span [centres_us[i], centres_us[i + 1]).  `seed`
-        also seeds the no-event subsampling.  The other arguments are the constructor's."""
+        also seeds the no-event subsampling.  The other arguments are the constructor's.
+
+        `viz_dir`: the directory (made if missing) that takes every window's accumulation images as the reference writes
+        them (provider.py:1356-1359, loaded_events_undist_viz): `<name>.png` in sensor coordinates and, when the stream has
+        a map, `<name>_undist.png` in rectified ones, of stream.accumulation_image.  The reference writes the array through
+        cv2.imwrite, which takes it as BGR: the files hold it with the channels reversed (negative events blue, positive
+        red).  `viz_names`: one name per window, the reference's frame indices as "%06d"; default "%06d" % i."""
         centres = [float(c) for c in centres_us]
         if len(centres) < 2:
             raise ValueError("EventSampler.from_stream: two window borders at least")
+        if viz_dir is not None:
+            import os
+            from .evaluate import write_png
+            names = ["%06d" % i for i in range(len(centres) - 1)] if viz_names is None else \
+                [n if isinstance(n, str) else "%06d" % int(n) for n in viz_names]
+            if len(names) != len(centres) - 1:
+                raise ValueError(f"EventSampler.from_stream: {len(names)} viz_names for {len(centres) - 1} windows")
+            os.makedirs(viz_dir, exist_ok=True)
         generator = None
         if seed is not None:
             generator = torch.Generator(device=stream.device).manual_seed(int(seed))
@@ -434,6 +448,12 @@ class EventSampler:
             else:
                 tab = stream.tables(win[0], win[1])
             tables.append(tab)
+            if viz_dir is not None:
+                for rectified, suffix in ((False, ""), (True, "_undist")):
+                    if rectified and stream.rectify_map is None:
+                        continue
+                    img = stream.accumulation_image(win[0], win[1], rectified=rectified)
+                    write_png(os.path.join(viz_dir, names[i] + suffix + ".png"), img.flip(-1).cpu().numpy())
         return cls(tables, track, intrinsics_evs, batch_size_evs, accumulate_evs, acc_max_num_evs,
                    no_events if negative_event_sampling else None, frames, seed)
 

@@ -81,7 +81,10 @@ const char* enerf_last_error(void);
  *     Still 13: enerf_background_forward / _backward added (the background model in one launch each way, DESIGN.md
  *     4.21) -- new symbols, nothing existing changed.
  *     Still 13: enerf_debug_event_segment_sort added (a testing aid: the segment sorts of enerf_event_tables_fill on
- *     segments of the caller's choice) -- a new symbol, nothing existing changed. */
+ *     segments of the caller's choice) -- a new symbol, nothing existing changed.
+ *     Still 13: enerf_event_pixel_stats, enerf_event_accumulation_image, enerf_event_count_moments, enerf_event_hot_mask
+ *     and enerf_event_stream_compact_workspace / _compact added (pixel counts, accumulation images, hot pixels and the
+ *     stream without them) -- new symbols, nothing existing changed. */
 #define ENERF_ABI_VERSION 13
 int enerf_abi_version(void);
 /* The library keeps grow-only scratch buffers per device (march chunk log, grid-backward record lists, ...).  Growing one
@@ -789,6 +792,45 @@ int enerf_no_event_coords(const int64_t* pixels, uint32_t n, const float* rect, 
  * as i64 [P] each (the num_at_xy / first_at_xy of _fill). */
 int enerf_debug_event_segment_sort(uint32_t* idx, uint32_t N, const uint32_t* num, const uint32_t* first, uint32_t P,
                                    void* workspace, enerf_stream_t stream);
+
+/* The loader's side of the same stream (csrc/event_stats.hip): per-pixel counts, the accumulation images
+ * of utils/plot_utils.py render_ev_accumulation (nerf/provider.py:227-230, :313-316), a hot-pixel mask, and the stream
+ * without the events of masked pixels.  x, y, t, p as above; windows [first, last) of 1 .. 2^30 events; H * W <= 2^26,
+ * H, W <= 65536.  Integer work: every output has the same bits on every run.
+ *
+ * enerf_event_pixel_stats: one pass over the window.  Per event, its coordinates compared with W, H BEFORE anything is
+ * indexed (an event outside the sensor is skipped and counted in *bad); then counts[y][x][p > 0 ? 1 : 0] += 1 (counts i32
+ * [H, W, 2]: polarity -1, polarity +1) and, where the arrays are given, last_sensor[y][x] = max(., i + 1) with i the
+ * event's index in the window, and last_rect[(int) yr][(int) xr] = max(., i + 1) with (xr, yr) = rect[y][x][0 .. 1] (f32
+ * [H, W, 2]) kept only if xr >= 0 && yr >= 0 && xr < W && yr < H in fp32 (false for NaN), truncated.  last_sensor,
+ * last_rect u32 [H, W] or NULL; 0 = no event.  last_rect needs rect.  The call zeroes counts, the arrays given and *bad
+ * (u64 [1]) first.  counts, rect and bad 8-byte aligned. */
+int enerf_event_pixel_stats(const uint16_t* x, const uint16_t* y, const int8_t* p, uint64_t first, uint64_t last, uint32_t H,
+                            uint32_t W, const float* rect, int32_t* counts, uint32_t* last_sensor, uint32_t* last_rect,
+                            uint64_t* bad, enerf_stream_t stream);
+/* A last-event array of enerf_event_pixel_stats on the same window to the picture: image u8 [H, W, 3], 4-byte aligned;
+ * a cell without an event (255, 255, 255), one whose last event has p <= 0 (255, 0, 0), p > 0 (0, 0, 255).  An entry
+ * above last - first reads nothing and is drawn as no event. */
+int enerf_event_accumulation_image(const uint32_t* last_event, const int8_t* p, uint64_t first, uint64_t last, uint32_t H,
+                                   uint32_t W, uint8_t* image, enerf_stream_t stream);
+/* moments u64 [3] = n, S, Q: the pixels with c > 0, the sum of c and the sum of c * c, c = counts[y][x][0] +
+ * counts[y][x][1] (each read as u32).  An integer reduction: any order gives the same bits.  The call zeroes moments
+ * first.  counts and moments 8-byte aligned. */
+int enerf_event_count_moments(const int32_t* counts, uint32_t H, uint32_t W, uint64_t* moments, enerf_stream_t stream);
+/* mask u8 [H, W] = c > threshold (1 / 0), every byte written; report u64 [2] = the number of such pixels and the sum of
+ * their c.  The call zeroes report first.  counts and report 8-byte aligned. */
+int enerf_event_hot_mask(const int32_t* counts, uint32_t H, uint32_t W, uint64_t threshold, uint8_t* mask, uint64_t* report,
+                         enerf_stream_t stream);
+/* The stream without the events of masked pixels, order kept: a keep flag per event (on the sensor -- compared before
+ * the mask is indexed -- and mask[y][x] == 0; mask u8 [H, W]), the exclusive scan of the flags, and x, y, t, p of every
+ * kept event written at its scanned position.  The outputs hold n_events entries each (1 .. 2^30); entries from the kept
+ * count on are not written.  report u32 [2] on the device = the kept count, the events outside the sensor (dropped);
+ * the call zeroes it first.  _workspace: *bytes = the scratch buffer of a call on n_events events (4-byte aligned,
+ * contents arbitrary, free once the launches have run). */
+int enerf_event_stream_compact_workspace(uint64_t n_events, uint64_t* bytes);
+int enerf_event_stream_compact(const uint16_t* x, const uint16_t* y, const int64_t* t, const int8_t* p, uint64_t n_events,
+                               uint32_t H, uint32_t W, const uint8_t* mask, void* workspace, uint16_t* x_out,
+                               uint16_t* y_out, int64_t* t_out, int8_t* p_out, uint32_t* report, enerf_stream_t stream);
 
 /* The event loss of Trainer.train_step_events (nerf/utils.py:499-516, C_thres != -1) and its gradient with respect to
  * the two rendered images, one launch: image1 / image2 [N,3] fp32, pols [N] -> delta [N,1] (use_luma) or [N,3],
